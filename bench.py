@@ -15,9 +15,13 @@ contracted per step, sharded over the ranks by index slicing: slice labels and p
 (`dist.sliced_plan`), every rank runs its share of the slices as replicas of one plan on its GPU and the
 partial results in split format are joined by ONE all_gather + log-sum-exp combine (strong scaling).
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the K steps and
+prints the headline; ``--full`` adds everything else the benchmark measures or checks, each outside the timed region
+except the HIP events of its first ``--event-passes`` steps:
   roofline     - dominant kernel: algorithmic flop (or bytes) / HIP-event duration vs the MFMA (or HBM) peak
   cpu_baseline - the NumPy oracle on the same network/path on this box's host cores (N=1 only)
+  device info, the R = 1 / 8 / 64 latency figures and the mps secondaries (batched MPS, PEPS, other configs).
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0's networks) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -82,7 +86,15 @@ def parse_args():
                          "own path search returns for this network (exploration; the workload label says so)")
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32",
                     help="f32 = the BASELINE metric; f64 = the same workload in double precision (secondary)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: roofline and per-step times (HIP "
+                         "events in the first timed steps), device info, CPU baseline with oracle parity, latency "
+                         "figures and the mps secondaries (batched MPS, PEPS, configs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_steps and not args.full:
+        ap.error("--dump-steps needs --full (the per-step times come from the HIP events that --full records)")
     if args.bond is None:
         args.bond = 256 if args.config == "mps" else 8
     return args
@@ -163,11 +175,11 @@ def main():
         result = run_peps(args, world, rank, local_rank, backend, dev)
     else:
         result = run_mps(args, world, rank, local_rank, backend, dev)
-        if args.with_batched and args.dtype == "f32":
+        if args.full and args.with_batched and args.dtype == "f32":
             batched_secondary(args, result, world, rank, backend, dev)
-        if args.with_peps and args.dtype == "f32":
+        if args.full and args.with_peps and args.dtype == "f32":
             peps_secondary(args, result, world, rank, local_rank, backend, dev)
-        if args.with_configs and args.dtype == "f32" and world == 1:
+        if args.full and args.with_configs and args.dtype == "f32" and world == 1:
             configs_secondary(args, result, world, rank, backend, dev)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -496,6 +508,7 @@ def peps_secondary(args, result, world, rank, local_rank, backend, dev):
             a2 = copy.copy(args)
             a2.rows, a2.cols, a2.bond, a2.slices, a2.max_intermediate = 8, 8, bond, slices, max_int
             a2.steps, a2.warmup, a2.no_cpu_baseline, a2.dump_steps, a2.event_passes = steps, warmup, True, None, 1
+            a2.dump_outputs = None             # the dumped outputs are the headline's
             a2.single_gpu_reference = True
             a2.cross_check = bond == 16        # D = 16 has no CPU oracle: two different slicings must agree
             try:
@@ -611,21 +624,26 @@ def run_mps(args, world, rank, local_rank, backend, dev):
     sync_all()
 
     # ---- timed region: exactly K steps --------------------------------------------------
-    # HIP events around every step's kernels, on the executor's stream, for the first passes of the
+    # --full: HIP events around every step's kernels, on the executor's stream, for the first passes of the
     # timed region (sampling keeps the event overhead out of most of the measurement)
-    ex.set_timing(min(args.steps, args.event_passes))
+    if args.full:
+        ex.set_timing(min(args.steps, args.event_passes))
     sync_all()
-    sampler = PowerSampler(dev) if rank == 0 else None   # sysfs reads on a host thread: clock and power WHILE timed
+    # sysfs reads on a host thread: clock and power WHILE timed
+    sampler = PowerSampler(dev) if rank == 0 and args.full else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         launch()
     sync_all()
     elapsed = time.perf_counter() - t0
     under_load = sampler.stop() if sampler else {}
-    step_ms_last = ex.step_ms().astype(np.float64)  # per-step mean over the event-bracketed passes
-    ex.set_timing(0)
+    if args.full:
+        step_ms_last = ex.step_ms().astype(np.float64)  # per-step mean over the event-bracketed passes
+        ex.set_timing(0)
     logs = np.concatenate([g.fetch_log_scale() for g in groups])
     t_hat = out[:, 0].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, t_hat=out.cpu().numpy().reshape((R,) + tuple(plan.out_shape)), log_scale=logs)
 
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
@@ -636,6 +654,34 @@ def run_mps(args, world, rank, local_rank, backend, dev):
     value = total_contractions / elapsed
     flops_per = plan.flops
     tflops = value * flops_per / 1e12
+    workload = f"mps_overlap_{args.sites}sites_D{args.bond}_d{args.phys}_{args.path}_R{R}"
+
+    result = {
+        "metric": (f"contractions/sec (MPS-{args.sites} overlap, bond={args.bond}, phys={args.phys}, "
+                   f"{'fp64' if f64 else 'fp32'}, stabilised split format)"),
+        "value": round(value, 2),
+        "unit": "contractions/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic (standard normal / 16, on-device generator, seeds 3+replica)",
+        "config": {
+            "workload": workload,
+            "replicas_per_gpu": R,
+            "steps_per_contraction": plan.n_steps,
+            "flop_per_contraction": flops_per,
+            "bytes_min_per_contraction": plan.bytes_min,
+            "parallelism": f"replicas x{world}",
+        },
+        "achieved_tflops": round(tflops, 3),
+    }
+    if not args.full:
+        return result if rank == 0 else None
 
     if args.dump_steps and rank == 0:
         with open(args.dump_steps, "w") as fh:
@@ -665,7 +711,6 @@ def run_mps(args, world, rank, local_rank, backend, dev):
     achieved = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
     mfma_ms = sum(d["ms"] for k, d in by_kernel.items() if k[0] in (2, 3))
     mfma_flops = sum(d["flops"] for k, d in by_kernel.items() if k[0] in (2, 3))
-    workload = f"mps_overlap_{args.sites}sites_D{args.bond}_d{args.phys}_{args.path}_R{R}"
     traffic, traffic_source = pmc_traffic(workload, kernel_label(dom_key))
     # algorithmic bytes of one launch of the dominant kernel: every operand and the output once
     dom_info = next(info for s_, info in enumerate(infos)
@@ -699,33 +744,8 @@ def run_mps(args, world, rank, local_rank, backend, dev):
         "end_to_end_tflops": round(tflops / world, 3),
         "end_to_end_frac": round(tflops / world / peak, 4),
     }
-
-    result = {
-        "metric": (f"contractions/sec (MPS-{args.sites} overlap, bond={args.bond}, phys={args.phys}, "
-                   f"{'fp64' if f64 else 'fp32'}, stabilised split format)"),
-        "value": round(value, 2),
-        "unit": "contractions/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.dtype,
-        "data": "synthetic (standard normal / 16, on-device generator, seeds 3+replica)",
-        "config": {
-            "workload": workload,
-            "replicas_per_gpu": R,
-            "steps_per_contraction": plan.n_steps,
-            "flop_per_contraction": flops_per,
-            "bytes_min_per_contraction": plan.bytes_min,
-            "parallelism": f"replicas x{world}",
-        },
-        "achieved_tflops": round(tflops, 3),
-        "roofline": roofline,
-        "device": dict(device_info(dev), **under_load),
-    }
+    result["roofline"] = roofline
+    result["device"] = dict(device_info(dev), **under_load)
     # context, not the graded fraction: the timed region runs at the board's power cap, below the 2.4 GHz the
     # nominal peak assumes; the same kernel figure against the peak at the clock that was actually held
     if under_load.get("sclk_under_load_mhz"):
@@ -848,17 +868,20 @@ def run_peps(args, world, rank, local_rank, backend, dev):
     sync_all()
 
     # ---- timed region: exactly K contractions, join included -------------------------------
-    timed_passes = min(args.steps, args.event_passes)
+    # (--full: HIP events around the launches of the first --event-passes contractions)
+    timed_passes = min(args.steps, args.event_passes) if args.full else 0
     for x, st in zip(execs, stages):
         x.set_timing(timed_passes * st[3])
     sync_all()
-    sampler = PowerSampler(dev) if rank == 0 else None
+    sampler = PowerSampler(dev) if rank == 0 and args.full else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         t_hat, log_scale = sc.run()
     sync_all()
     elapsed = time.perf_counter() - t0
     under_load = sampler.stop() if sampler else {}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, t_hat=np.reshape(t_hat, -1), log_scale=np.reshape(log_scale, -1))
     # per step: mean over the recorded launches (--event-passes 0, counter-collection runs: none recorded)
     stage_ms = [x.step_ms().astype(np.float64) if timed_passes else np.zeros(st[0].plan.n_steps) for x, st in zip(execs, stages)]
     for x in execs:
@@ -887,7 +910,7 @@ def run_peps(args, world, rank, local_rank, backend, dev):
     sizes, n_total, n_mine, sc_R, sc_outer = sc.sizes, sc.n_total, len(sc.my_slices), sc.R, getattr(sc, "outer", 0)
     sc_unsliced = len(getattr(sc, "unsliced", ()))
     cpu_check = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_check = peps_cpu_baseline(sc, einstr, ops, labels, path, args.cpu_seconds)
     del sc, execs, stages
     torch.cuda.empty_cache()
@@ -908,60 +931,6 @@ def run_peps(args, world, rank, local_rank, backend, dev):
     flop_sliced = float(sum(sd.flops * n for sd, n in zip(stage_data, n_eval_total)))
     tflops = value * flop_sliced / 1e12
 
-    # ---- roofline of the dominant kernel on rank 0 (per launch of R evaluations, HIP-event durations) ---------
-    # algorithmic bytes of a step: both operands and the output once, from the step's own einsum string
-    by_kernel, dump = {}, []
-    for k_, (sd, ms_) in enumerate(zip(stage_data, stage_ms)):
-        infos, tiles, R_, chunks_ = sd.infos, sd.tiles, sd.R, sd.launches
-        for s_, (info, step_str) in enumerate(zip(infos, sd.step_strs)):
-            lhs, out = step_str.split("->")
-            nbytes = 4 * sum(int(np.prod([sizes[x] for x in set(t)])) if t else 1 for t in lhs.split(",") + [out])
-            key = (info["kernel"], info["mode_a"], info["mode_b"], tiles[s_][0], tiles[s_][1])
-            d = by_kernel.setdefault(key, {"ms": 0.0, "flops": 0.0, "bytes": 0.0, "launches": 0})
-            d["ms"] += ms_[s_] * chunks_               # per contraction (rank 0): the step's mean launch x its launches
-            d["flops"] += info["flops"] * R_ * chunks_
-            d["bytes"] += nbytes * R_ * chunks_
-            d["launches"] += chunks_
-            dump.append(dict(info, stage=k_, ms=float(ms_[s_]), bytes=nbytes, replicas=R_, launches=chunks_,
-                             tile=list(tiles[s_]), einsum=step_str))
-    if args.dump_steps:
-        with open(args.dump_steps, "w") as fh:
-            json.dump(dump, fh)
-    dom_key = max(by_kernel, key=lambda k: by_kernel[k]["ms"])
-    dom = by_kernel[dom_key]
-    mfma = dom_key[0] in (2, 3)
-    # an MFMA step below the ridge (157.3 TFLOP/s / 8 TB/s = 19.7 flop/B) is priced against HBM as well
-    ai = dom["flops"] / max(dom["bytes"], 1.0)
-    hbm_bound = (not mfma) or ai < PEAK_F32_MFMA_TFLOPS / PEAK_HBM_TBS
-    sec = dom["ms"] * 1e-3
-    ach_tf = dom["flops"] / sec / 1e12 if sec > 0 else 0.0
-    ach_tb = dom["bytes"] / sec / 1e12 if sec > 0 else 0.0
-    total_ms = sum(d["ms"] for d in by_kernel.values())
-    roofline = {
-        "bound": "hbm" if hbm_bound else "mfma",
-        "kernel": kernel_label(dom_key),
-        "achieved": round(ach_tb * 1e3 if hbm_bound else ach_tf, 3),
-        "peak": PEAK_HBM_TBS * 1e3 if hbm_bound else PEAK_F32_MFMA_TFLOPS,
-        "unit": "GB/s" if hbm_bound else "TFLOP/s",
-        "frac": round(ach_tb / PEAK_HBM_TBS if hbm_bound else ach_tf / PEAK_F32_MFMA_TFLOPS, 4),
-        "traffic": None,
-        "traffic_source": None,
-        "arithmetic_intensity_flop_per_byte": round(ai, 2),
-        "launches_per_contraction": dom["launches"],
-        "avg_launch_us": round(dom["ms"] * 1e3 / max(dom["launches"], 1), 2),
-        "share_of_device_time": round(dom["ms"] / total_ms, 4) if total_ms > 0 else None,
-        "algorithmic_bytes_per_launch": dom["bytes"] / max(dom["launches"], 1),
-        "flop_per_launch": dom["flops"] / max(dom["launches"], 1),
-        "timing_mode": (f"HIP events on the executor's stream around every launch of the first {timed_passes} timed "
-                        f"steps (eager launches; later steps replay the same kernels as one hipGraph), rank 0"),
-        "kernels": [
-            {"kernel": kernel_label(k), "launches": d["launches"], "ms": round(d["ms"], 4),
-             "tflops": round(d["flops"] / (d["ms"] * 1e-3) / 1e12, 2) if d["ms"] > 0 else None,
-             "tb_per_s": round(d["bytes"] / (d["ms"] * 1e-3) / 1e12, 3) if d["ms"] > 0 else None}
-            for k, d in sorted(by_kernel.items(), key=lambda kv: -kv[1]["ms"])],
-        "end_to_end_tflops": round(tflops, 3),
-        "end_to_end_frac_of_mfma_peak_per_gpu": round(tflops / world / PEAK_F32_MFMA_TFLOPS, 4),
-    }
     result = {
         "metric": (f"contractions/sec ({rows}x{cols} PEPS, bond={bond}, phys=2, closed, fp32, stabilised split "
                    f"format, index-sliced over the ranks, one all_gather join)"),
@@ -1003,9 +972,64 @@ def run_peps(args, world, rank, local_rank, backend, dev):
         "collectives": {"process_group": bool(pg), "backend": (dist.get_backend() if pg else None), "world": world,
                         "join_all_gather_per_contraction": bool(world > 1 or cdist.join_alone())},
         "result": {"t_hat": float(t_hat), "log_scale": float(log_scale)},
-        "roofline": roofline,
-        "device": dict(device_info(dev), **under_load),
     }
+    if args.full:
+        # ---- roofline of the dominant kernel on rank 0 (per launch of R evaluations, HIP-event durations) ---------
+        # algorithmic bytes of a step: both operands and the output once, from the step's own einsum string
+        by_kernel, dump = {}, []
+        for k_, (sd, ms_) in enumerate(zip(stage_data, stage_ms)):
+            infos, tiles, R_, chunks_ = sd.infos, sd.tiles, sd.R, sd.launches
+            for s_, (info, step_str) in enumerate(zip(infos, sd.step_strs)):
+                lhs, out = step_str.split("->")
+                nbytes = 4 * sum(int(np.prod([sizes[x] for x in set(t)])) if t else 1 for t in lhs.split(",") + [out])
+                key = (info["kernel"], info["mode_a"], info["mode_b"], tiles[s_][0], tiles[s_][1])
+                d = by_kernel.setdefault(key, {"ms": 0.0, "flops": 0.0, "bytes": 0.0, "launches": 0})
+                d["ms"] += ms_[s_] * chunks_               # per contraction (rank 0): the step's mean launch x its launches
+                d["flops"] += info["flops"] * R_ * chunks_
+                d["bytes"] += nbytes * R_ * chunks_
+                d["launches"] += chunks_
+                dump.append(dict(info, stage=k_, ms=float(ms_[s_]), bytes=nbytes, replicas=R_, launches=chunks_,
+                                 tile=list(tiles[s_]), einsum=step_str))
+        if args.dump_steps:
+            with open(args.dump_steps, "w") as fh:
+                json.dump(dump, fh)
+        dom_key = max(by_kernel, key=lambda k: by_kernel[k]["ms"])
+        dom = by_kernel[dom_key]
+        mfma = dom_key[0] in (2, 3)
+        # an MFMA step below the ridge (157.3 TFLOP/s / 8 TB/s = 19.7 flop/B) is priced against HBM as well
+        ai = dom["flops"] / max(dom["bytes"], 1.0)
+        hbm_bound = (not mfma) or ai < PEAK_F32_MFMA_TFLOPS / PEAK_HBM_TBS
+        sec = dom["ms"] * 1e-3
+        ach_tf = dom["flops"] / sec / 1e12 if sec > 0 else 0.0
+        ach_tb = dom["bytes"] / sec / 1e12 if sec > 0 else 0.0
+        total_ms = sum(d["ms"] for d in by_kernel.values())
+        roofline = {
+            "bound": "hbm" if hbm_bound else "mfma",
+            "kernel": kernel_label(dom_key),
+            "achieved": round(ach_tb * 1e3 if hbm_bound else ach_tf, 3),
+            "peak": PEAK_HBM_TBS * 1e3 if hbm_bound else PEAK_F32_MFMA_TFLOPS,
+            "unit": "GB/s" if hbm_bound else "TFLOP/s",
+            "frac": round(ach_tb / PEAK_HBM_TBS if hbm_bound else ach_tf / PEAK_F32_MFMA_TFLOPS, 4),
+            "traffic": None,
+            "traffic_source": None,
+            "arithmetic_intensity_flop_per_byte": round(ai, 2),
+            "launches_per_contraction": dom["launches"],
+            "avg_launch_us": round(dom["ms"] * 1e3 / max(dom["launches"], 1), 2),
+            "share_of_device_time": round(dom["ms"] / total_ms, 4) if total_ms > 0 else None,
+            "algorithmic_bytes_per_launch": dom["bytes"] / max(dom["launches"], 1),
+            "flop_per_launch": dom["flops"] / max(dom["launches"], 1),
+            "timing_mode": (f"HIP events on the executor's stream around every launch of the first {timed_passes} timed "
+                            f"steps (eager launches; later steps replay the same kernels as one hipGraph), rank 0"),
+            "kernels": [
+                {"kernel": kernel_label(k), "launches": d["launches"], "ms": round(d["ms"], 4),
+                 "tflops": round(d["flops"] / (d["ms"] * 1e-3) / 1e12, 2) if d["ms"] > 0 else None,
+                 "tb_per_s": round(d["bytes"] / (d["ms"] * 1e-3) / 1e12, 3) if d["ms"] > 0 else None}
+                for k, d in sorted(by_kernel.items(), key=lambda kv: -kv[1]["ms"])],
+            "end_to_end_tflops": round(tflops, 3),
+            "end_to_end_frac_of_mfma_peak_per_gpu": round(tflops / world / PEAK_F32_MFMA_TFLOPS, 4),
+        }
+        result["roofline"] = roofline
+        result["device"] = dict(device_info(dev), **under_load)
     if cpu_check is not None:
         result["cpu_baseline"] = cpu_check
         if rep["unsliced_largest_intermediate"] <= 2 ** 28:
@@ -1184,6 +1208,17 @@ def peps_unsliced_check(einstr, shapes, ops, t_sliced, c_sliced, device):
     rel = abs(np.exp(c_sliced - c_u) * (t_sliced * t_u) - 1.0)
     return {"ok": bool(rel <= 1e-3), "rel_diff": float(rel), "unsliced": [t_u, c_u], "sliced": [t_sliced, c_sliced],
             "unsliced_flop": bc.plan.flops}
+
+
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, in float32 or float64 (the arrays are a few kB: the results of
+    R closed networks, or of one)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def pmc_traffic(workload, kernel):

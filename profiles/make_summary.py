@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Turn raw rocprofv3 outputs (gpurun_out/, scratch) into the committed per-round summaries.
+"""Turn raw rocprofv3 outputs (bench_out/ of tools/regen_profiles.sh) into the committed per-round summaries.
 
-    python profiles/make_summary.py r02 gpurun_out/prof_r02 gpurun_out/pmc_fetch gpurun_out/pmc_write gpurun_out/pmc_sq \
-        gpurun_out/bench_default.json
+    python profiles/make_summary.py r02 bench_out/prof_r02 bench_out/pmc_fetch bench_out/pmc_write bench_out/pmc_sq \
+        bench_out/bench_default.json
 
-The last argument is the bench line of the same command in the same gpurun call: its workload name and dominant-kernel
+The last argument is the `--full` bench line of the same command in the same session: its workload name and dominant-kernel
 label are stored next to the counters, and bench.py attaches `roofline.traffic` only to a run that matches both.
 
 Writes profiles/<round>_kernel_stats.csv (rocprofv3 --kernel-trace --stats, ctn kernels only),

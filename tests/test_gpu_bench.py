@@ -1,11 +1,13 @@
 """bench.py end to end on a small instance of the metric's network: the JSON contract of the driver
-(one line; metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling / dtype / config.workload)
-plus the `roofline` and `cpu_baseline` objects, and the oracle check that the N = 1 run carries."""
+(one line; metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling / dtype / config.workload),
+with `--full` the `roofline` and `cpu_baseline` objects and the oracle check that the N = 1 run carries, and the
+outputs `--dump-outputs` writes."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.helpers import ROOT
@@ -14,9 +16,10 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("dtype", ["f32", "f64"])
-def test_bench_line_contract(dtype):
+def test_bench_line_contract(dtype, tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--sites", "12", "--bond", "64", "--replicas", "8", "--cpu-seconds", "0.5", "--dtype", dtype]
+           "--sites", "12", "--bond", "64", "--replicas", "8", "--cpu-seconds", "0.5", "--dtype", dtype, "--full",
+           "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -35,6 +38,12 @@ def test_bench_line_contract(dtype):
     cpu = r["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["value"] > 0 and cpu["cores"] >= 1 and cpu["sample"]
     assert cpu["parity_vs_gpu"]["ok"] is True          # replica 0 of this very run against the oracle
+    # the dumped outputs are what the timed path returned: replica 0 and the last one are those the oracle checked
+    t_hat, log_scale = np.load(tmp_path / "t_hat.npy"), np.load(tmp_path / "log_scale.npy")
+    assert t_hat.shape == (8,) and t_hat.dtype == (np.float32 if dtype == "f32" else np.float64)
+    assert log_scale.shape == (8,) and log_scale.dtype == np.float64
+    for r_, pv in ((0, cpu["parity_vs_gpu"]), (7, cpu["parity_vs_gpu"]["last_replica"])):
+        assert [float(t_hat[r_]), float(log_scale[r_])] == pv["gpu"]
     assert r["device"]["compute_units"] > 0
     if dtype == "f32":   # the secondaries ride on the fp32 line and never replace it
         b = r["batched_mps"]
@@ -57,3 +66,31 @@ def test_bench_line_contract(dtype):
         # the hyperedge route and the materialised delta hub give the same entry (same factor matrices)
         a, b_ = cfgs["cfg4_i_cp_hyper"]["spot_check_vs_definition_f64"], cfgs["cfg4_iii_tucker_delta_hub"]["spot_check_vs_definition_f64"]
         assert a["want"] == b_["want"] and abs(a["got"] - b_["got"]) <= 1e-3 * abs(a["want"]) + 1e-9
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain run (no `--full`): the headline keys and none of the extra measurements; `--steps` sets the timed
+    steps, and `--dump-outputs` writes the last timed step's results, the same in a second run with the same arguments
+    (seeded inputs)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+           "--sites", "12", "--bond", "64", "--replicas", "8"]
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600,
+                             cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["unit"] == "contractions/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+        assert r["steps"] == 4 and r["warmup"] == 1 and r["value"] > 0
+        assert abs(r["ms_per_step"] - 8 * 1e3 / r["value"]) <= 1e-3 * r["ms_per_step"] + 1e-3
+        assert r["metric"].startswith("contractions/sec (MPS-12 overlap, bond=64")
+        for key in ("roofline", "cpu_baseline", "latency", "device", "batched_mps", "peps_strong_scaling", "configs"):
+            assert key not in r, key
+        dumps.append((np.load(tmp_path / run / "t_hat.npy"), np.load(tmp_path / run / "log_scale.npy")))
+    (t_a, c_a), (t_b, c_b) = dumps
+    assert t_a.shape == (8,) and t_a.dtype == np.float32 and c_a.shape == (8,) and c_a.dtype == np.float64
+    assert np.all(np.abs(t_a) == 1.0) and np.all(np.isfinite(c_a))      # closed networks: (sign, log|value|)
+    np.testing.assert_array_equal(t_a, t_b)
+    np.testing.assert_allclose(c_a, c_b, rtol=0, atol=1e-4)

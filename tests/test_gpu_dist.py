@@ -88,7 +88,7 @@ def test_bench_peps_two_ranks_rehearsal():
     carries the strong-scaling contract, the roofline of the dominant kernel and a finite, correct value."""
     env = dict(os.environ, CTN_BENCH_BACKEND="gloo", CTN_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     common = ["--config", "peps", "--rows", "4", "--cols", "4", "--bond", "4", "--slices", "8", "--steps", "3",
-              "--warmup", "2", "--cpu-seconds", "2"]
+              "--warmup", "2", "--cpu-seconds", "2", "--full"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common, env=env, cwd=ROOT,
                          capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -293,7 +293,7 @@ def test_bench_default_two_ranks_rehearsal():
     env = dict(os.environ, CTN_BENCH_BACKEND="gloo", CTN_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--sites", "12", "--bond", "64", "--replicas", "8", "--peps-bonds", "8"]
+           "--sites", "12", "--bond", "64", "--replicas", "8", "--peps-bonds", "8", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -605,7 +605,7 @@ def test_bench_peps_under_a_one_rank_launcher_over_rccl():
     the join all run on RCCL; the line says so and its value agrees with the unsliced network."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "peps", "--bond", "8",
-           "--steps", "5", "--warmup", "2", "--cpu-seconds", "3"]
+           "--steps", "5", "--warmup", "2", "--cpu-seconds", "3", "--full"]
     out = subprocess.run(cmd, env=_one_rank_launcher_env(), cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -3,7 +3,7 @@
 python - <<PY
 import json, subprocess, sys, os
 out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--replicas", "8", "--sites", "12", "--bond", "64",
-                      "--no-peps", "--no-batched", "--no-cpu-baseline", "--no-latency"], capture_output=True, text=True)
+                      "--full", "--no-peps", "--no-batched", "--no-cpu-baseline", "--no-latency"], capture_output=True, text=True)
 line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
 for k, v in line["configs"].items():
     if k.startswith("cfg4"):
