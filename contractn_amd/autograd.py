@@ -1,0 +1,415 @@
+"""Reverse mode of ``contract()`` on device tensors: a ``torch.autograd.Function`` ("Autograd").
+
+The reference's torch backend builds an ordinary autograd graph through every ``stabilize()`` (reference
+einsum.py:9-21, :89-107, :338-391).  Here the forward is the engine's own fused run, unchanged, and the backward
+recomputes the intermediates step by step and walks the path in reverse with one-step native plans:
+
+* every cotangent is kept in split form ``G = G_hat e^g`` with ``g`` a float64 device register, so an intermediate
+  cotangent is never formed at full scale (a result whose plain value is ``inf`` still has finite gradients);
+* below a rescaled step only the plain value ``Z_k = Z_hat_k e^{z_k}`` matters and the rule is plain pairwise backprop:
+  ``G_A = pair_grad(G_C, Z_B)``, i.e. ``G_hat_A = contract(G_hat_C, Z_hat_B)`` with ``g_A = g_C + z_B + log(rescale)``;
+* the split outputs ``(T_hat, c)`` enter through ``ctn_grad_seed`` at the "frontier": the root when it was rescaled,
+  otherwise the rescaled steps nearest to it, above which cotangents of ``Z_hat`` pass through the unrescaled steps
+  and ``G_c`` goes down unchanged;
+* labels an operand sums on its own are not materialised (the gradient is constant along them) and a label repeated
+  in an operand is written on its diagonal only - both by ``ctn_grad_leaf``, which writes each gradient in the
+  operand's shape and dtype.
+
+Everything runs on torch's current stream (or one side stream when torch is on the legacy default stream, whose
+handle the engine cannot take); the backward waits on the host at most once - for the per-step rescale flags, only
+when the root of a split-format result was not rescaled.  Double backward is not supported (``once_differentiable``).
+"""
+import threading
+from collections import OrderedDict
+
+import numpy as np
+
+from . import einsum, engine
+
+# Cotangent contractions re-stabilise whenever their abs-sum is positive at all: a gradient has no "negligible" norm
+# (the forward's threshold, einsum.MIN_NORM, is the reference's and is kept for the recomputed forward steps).
+GRAD_MIN_NORM = 1e-30
+MAX_CACHED_SCHEDULES = 8
+
+
+def _canon(*label_lists):
+    """Relabel by first appearance: one-step plans of equal structure and shapes share a plan and an executor."""
+    m = {}
+    return tuple(tuple(m.setdefault(l, len(m)) for l in lab) for lab in label_lists)
+
+
+class BackwardSchedule:
+    """Host description of the reverse walk of one ``(contract_list, shapes, dtype, split_format)``.
+
+    ``steps[k] = (lhs, rhs | -1, out_labels)`` are the SSA steps of `einsum.lower_contraction_list`; ids ``0..n-1`` are
+    the operands, ``n + k`` the result of step ``k``.  ``labels[id]`` are the axis labels of every id (an operand may
+    repeat one), ``cot_labels[id]`` the labels its cotangent carries when its parent passes it down: the operand's
+    labels (each once) that the parent's cotangent or the sibling carries - the others are ``broadcast[id]``.
+    One-step native plans are built on first use and shared between steps of equal structure."""
+
+    def __init__(self, contract_list, shapes, dtype_name, split_format):
+        self.shapes = tuple(tuple(int(d) for d in s) for s in shapes)
+        self.dtype = np.dtype(dtype_name)
+        self.split_format = bool(split_format)
+        n = self.n_inputs = len(self.shapes)
+        in_labels, steps = einsum.lower_contraction_list(n, contract_list, self.shapes)
+        self.steps = [(int(a), int(b), tuple(out)) for a, b, out in steps]
+        self.n_steps = len(self.steps)
+        self.root = n + self.n_steps - 1
+        self.labels = [tuple(l) for l in in_labels]
+        self.size = {}
+        for lab, shp in zip(self.labels, self.shapes):
+            if len(lab) != len(shp):
+                raise ValueError(f"operand of shape {shp} does not match its {len(lab)} subscripts")
+            for l, d in zip(lab, shp):
+                self.size[l] = d
+        self.parent = {}
+        for k, (a, b, out) in enumerate(self.steps):
+            self.labels.append(out)
+            self.parent[a] = k
+            if b >= 0:
+                self.parent[b] = k
+        # structural cotangent labels, root down (steps are in topological order: walk them in reverse)
+        self.cot_labels = {self.root: self.labels[self.root]}
+        self.broadcast = {self.root: ()}
+        for k in reversed(range(self.n_steps)):
+            a, b, _out = self.steps[k]
+            gl = set(self.cot_labels[n + k])
+            for child, other in ((a, b), (b, a)):
+                if child < 0:
+                    continue
+                uniq = tuple(dict.fromkeys(self.labels[child]))
+                if other < 0:                   # a unary step passes its cotangent down as it is
+                    self.cot_labels[child] = self.cot_labels[n + k]
+                else:
+                    other_l = set(self.labels[other])
+                    self.cot_labels[child] = tuple(l for l in uniq if l in gl or l in other_l)
+                self.broadcast[child] = tuple(l for l in uniq if l not in self.cot_labels[child])
+        self._plans = {}
+        self._executors = {}
+        self._lock = threading.Lock()
+
+    # -- structure ----------------------------------------------------------------------------------------------
+    def shape_of(self, labels):
+        return tuple(self.size[l] for l in labels)
+
+    def needs(self, needs_input_grad):
+        """Per id: does any operand below it need a gradient?  (Subtrees that need none are skipped.)"""
+        need = [bool(x) for x in needs_input_grad] + [False] * self.n_steps
+        for k, (a, b, _out) in enumerate(self.steps):
+            need[self.n_inputs + k] = need[a] or (b >= 0 and need[b])
+        return need
+
+    def frontier(self, rescaled):
+        """Steps where the split-format seed applies, given whether each step was rescaled (``rescaled[k]``): the
+        root when rescaled, else the rescaled steps nearest to it on every path.  Plain output: no frontier."""
+        if not self.split_format:
+            return ()
+        front, todo = [], [self.root]
+        while todo:
+            i = todo.pop()
+            if i < self.n_inputs:
+                continue
+            k = i - self.n_inputs
+            if rescaled[k]:
+                front.append(k)
+                continue
+            a, b, _out = self.steps[k]
+            todo += [c for c in (a, b) if c >= 0]
+        return tuple(sorted(front))
+
+    # -- native plans ---------------------------------------------------------------------------------------------
+    def plan(self, in_labels, out_labels, min_norm, free_order=False):
+        """One-step plan ``in_labels[0] (, in_labels[1]) -> out_labels`` (cached; ``free_order``: the engine's
+        output axis order, read from ``plan.out_labels``).  Returns ``(plan, labels of its output in order)``."""
+        in_labels = [tuple(l) for l in in_labels]
+        shapes = tuple(self.shape_of(l) for l in in_labels)
+        key = (_canon(*in_labels, tuple(out_labels)), shapes, min_norm, free_order)
+        with self._lock:
+            hit = self._plans.get(key)
+            if hit is None:
+                canon = _canon(*in_labels, tuple(out_labels))
+                ins, out = list(canon[:-1]), canon[-1]
+                step = (0, 1 if len(ins) == 2 else -1, out)
+                hit = engine.Plan(self.dtype, ins, shapes, [step], stabilize=True, min_norm=min_norm,
+                                  free_output_order=free_order)
+                self._plans[key] = hit
+        # the plan works on canonical labels: translate its output order back
+        m = {}
+        for lab in list(in_labels) + [tuple(out_labels)]:
+            for l in lab:
+                m.setdefault(l, len(m))
+        back = {v: k for k, v in m.items()}
+        return hit, tuple(back[l] for l in hit.out_labels)
+
+    def executor(self, plan, device, stream):
+        key = (id(plan), device, stream, threading.get_ident())
+        with self._lock:
+            ex = self._executors.get(key)
+            if ex is None:
+                ex = engine.Executor(plan, replicas=1, device=device, stream=stream)
+                ex.set_rescale_mode(1)      # eager: one-step runs are never "suspect", nothing to fetch
+                self._executors[key] = ex
+        return ex
+
+    def close(self):
+        with self._lock:
+            exs, self._executors = list(self._executors.values()), {}
+        for ex in exs:
+            ex.close()
+
+
+_SCHEDULES = OrderedDict()
+_SCHEDULES_LOCK = threading.Lock()
+
+
+def backward_schedule(contract_list, shapes, dtype_name, split_format):
+    """Cached `BackwardSchedule` (like `einsum._native_plan`)."""
+    key = (contract_list, tuple(tuple(int(d) for d in s) for s in shapes), str(dtype_name), bool(split_format))
+    evicted = []
+    with _SCHEDULES_LOCK:
+        sch = _SCHEDULES.get(key)
+        if sch is not None:
+            _SCHEDULES.move_to_end(key)
+            return sch
+        sch = BackwardSchedule(contract_list, key[1], key[2], key[3])
+        _SCHEDULES[key] = sch
+        while len(_SCHEDULES) > MAX_CACHED_SCHEDULES:
+            evicted.append(_SCHEDULES.popitem(last=False)[1])
+    for old in evicted:
+        old.close()
+    return sch
+
+
+def clear_caches():
+    with _SCHEDULES_LOCK:
+        dropped = list(_SCHEDULES.values())
+        _SCHEDULES.clear()
+    for sch in dropped:
+        sch.close()
+
+
+_SIDE_STREAMS = {}
+
+
+def _stream_for(torch, dev):
+    """``(stream handle, side stream or None)``: torch's current stream, or - on the legacy default stream, which the
+    engine cannot take - one side stream per device ordered after it."""
+    cur = torch.cuda.current_stream(dev)
+    if cur.cuda_stream:
+        return cur.cuda_stream, None
+    side = _SIDE_STREAMS.get(dev.index)
+    if side is None:
+        side = _SIDE_STREAMS.setdefault(dev.index, torch.cuda.Stream(dev))
+    side.wait_stream(cur)
+    return side.cuda_stream, side
+
+
+# ---------------------------------------------------------------------------
+# the autograd Function
+# ---------------------------------------------------------------------------
+def contract_with_grad(plan, operands, dtype, plain, contract_list):
+    """`einsum._run_torch` for device operands of which some require grad: same values, plus a graph."""
+    import torch
+
+    for o in operands:
+        if o.requires_grad and o.dtype not in (torch.float32, torch.float64):
+            raise NotImplementedError(f"autograd of contract(): operands of {o.dtype} are not supported")
+    fn = _function(torch)
+    res = fn.apply((plan, np.dtype(dtype), bool(plain), contract_list), *operands)
+    if plain:
+        return res, None
+    return res
+
+
+_FN = []
+
+
+def _function(torch):
+    if _FN:
+        return _FN[0]
+    from torch.autograd.function import once_differentiable
+
+    class ContractFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, meta, *operands):
+            plan, dtype, plain, contract_list = meta
+            out, log_scale, resc, ops = einsum._run_torch_device(plan, operands, dtype, plain)
+            ctx.set_materialize_grads(False)
+            ctx.meta = meta
+            ctx.ops = ops
+            ctx.in_dtypes = [o.dtype for o in operands]
+            ctx.root_rescaled = bool(resc[plan.n_steps - 1] > 0) if len(resc) else True
+            if plain:
+                return out
+            return out, log_scale
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, *grads):
+            plan, dtype, plain, contract_list = ctx.meta
+            shapes = tuple(tuple(o.shape) for o in ctx.ops)
+            sch = backward_schedule(contract_list, shapes, dtype.name, not plain)
+            g_t = grads[0]
+            g_c = None if plain else grads[1]
+            inputs = _backward(torch, sch, ctx.ops, ctx.in_dtypes, ctx.needs_input_grad[1:], g_t, g_c,
+                               ctx.root_rescaled)
+            return (None,) + tuple(inputs)
+
+    _FN.append(ContractFunction)
+    return ContractFunction
+
+
+def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_rescaled):
+    """Gradients of every operand (None where not needed) - see the module docstring."""
+    dev = ops[0].device
+    tdt = ops[0].dtype
+    n, S = sch.n_inputs, sch.n_steps
+    n_ids = n + S
+    need = sch.needs(needs_input_grad)
+    stream, side = _stream_for(torch, dev)
+    devi = dev.index or 0
+    ctx_stream = torch.cuda.stream(side) if side is not None else _NullCtx()
+    with ctx_stream:
+        if side is not None:
+            for t in list(ops) + [x for x in (g_t, g_c) if x is not None]:
+                t.record_stream(side)
+
+        def dense(x):
+            if x is None:
+                return None
+            x = x.to(device=dev, dtype=tdt).contiguous()
+            return x.clone() if x.data_ptr() % 16 else x
+
+        g_t, g_c = dense(g_t), dense(g_c)
+        # float64 registers: z[id] (0 for operands), the log of one run, g of a cotangent, the seed's g, a zero
+        Z, LOG, G, SEED, ZERO = 0, n_ids, 2 * n_ids, 3 * n_ids, 4 * n_ids
+        regs = torch.zeros(4 * n_ids + 1, dtype=torch.float64, device=dev)
+        idx0 = torch.zeros(1, dtype=torch.int64, device=dev)
+        base, i0 = regs.data_ptr(), idx0.data_ptr()
+
+        def reg(i):
+            return base + 8 * i
+
+        def add(dst, own, kids):
+            ex_any.add_scales(reg(dst), reg(own), 1, [(reg(k), i0) for k in kids])
+
+        # 1. recompute Z_hat_k and z_k step by step (the root only where a split-format seed needs it)
+        zhat = {i: ops[i] for i in range(n)}
+        last = S if sch.split_format else S - 1
+        flags_host = None
+        if sch.split_format and not root_rescaled:
+            flags_host = torch.zeros(S, dtype=torch.float64, pin_memory=True)
+        ex_any = None
+        for k in range(last):
+            a, b, out = sch.steps[k]
+            ins = [sch.labels[a]] + ([sch.labels[b]] if b >= 0 else [])
+            plan, _ = sch.plan(ins, out, einsum.MIN_NORM)
+            ex = ex_any = sch.executor(plan, devi, stream)
+            buf = torch.empty(plan.out_shape, dtype=tdt, device=dev)
+            ex.enqueue([zhat[a].data_ptr()] + ([zhat[b].data_ptr()] if b >= 0 else []), [buf.data_ptr()])
+            ex.snapshot_scales(reg(LOG + n + k), 1, flags_host.data_ptr() + 8 * k if flags_host is not None else 0)
+            zhat[n + k] = buf
+            add(Z + n + k, LOG + n + k, [Z + a] + ([Z + b] if b >= 0 else []))
+        if ex_any is None:          # a one-step plain contraction: any executor of the stream runs the bookkeeping
+            a, b, out = sch.steps[0]
+            ins = [sch.labels[a]] + ([sch.labels[b]] if b >= 0 else [])
+            ex_any = sch.executor(sch.plan(ins, out, einsum.MIN_NORM)[0], devi, stream)
+        if flags_host is not None:
+            (side if side is not None else torch.cuda.current_stream(dev)).synchronize()   # the one host wait
+            rescaled = [bool(v > 0) for v in flags_host.tolist()]
+        else:
+            rescaled = [True] * S       # (split format: only the root's flag matters then, known from the forward)
+        frontier = set(sch.frontier(rescaled))
+        scratch = torch.empty(engine.GRAD_SCRATCH, dtype=torch.float64, device=dev) if frontier else None
+
+        # 2. the reverse walk: cot[id] = (buffer or None, labels, g register or None, below the frontier?)
+        cot = {sch.root: (g_t, sch.labels[sch.root], None, not sch.split_format)}
+        grads = [None] * n
+
+        def expand(buf, labels, full):
+            """A cotangent laid out exactly like Z_hat (labels ``full``): broadcast / reorder if needed."""
+            if buf is None or tuple(labels) == tuple(full):
+                return buf
+            shp = sch.shape_of(full)
+            dst = torch.empty(shp, dtype=tdt, device=dev)
+            ex_any.grad_leaf(sch.dtype, buf.data_ptr(), 0, shp, _src_strides(full, labels, sch),
+                             list(range(len(full))), sch.dtype, dst.data_ptr())
+            return dst
+
+        for k in reversed(range(S)):
+            i = n + k
+            if not need[i] or i not in cot:
+                continue
+            buf, lab, g, below = cot.pop(i)
+            if k in frontier:
+                full = sch.labels[i]
+                gh = expand(buf, lab, full)
+                out = torch.empty(sch.shape_of(full), dtype=tdt, device=dev)
+                ex_any.grad_seed(sch.dtype, zhat[i].data_ptr(), gh.data_ptr() if gh is not None else 0,
+                                 g_c.data_ptr() if g_c is not None else 0, reg(Z + i),
+                                 reg(g) if g is not None else 0, out.numel(), GRAD_MIN_NORM, out.data_ptr(),
+                                 reg(SEED + i), scratch.data_ptr())
+                buf, lab, g, below = out, full, SEED + i, True
+            a, b, _out = sch.steps[k]
+            for child, other in ((a, b), (b, a)):
+                if child < 0 or not need[child]:
+                    continue
+                if buf is None:
+                    cot[child] = (None, (), None, below)
+                    continue
+                if other < 0:                       # unary step: the cotangent passes down as it is
+                    cot[child] = (buf, lab, g, below)
+                    continue
+                gl = sch.cot_labels[child]
+                fixed = sch.split_format and not below and child >= n and (child - n) in frontier
+                plan, out_l = sch.plan([lab, sch.labels[other]], gl, GRAD_MIN_NORM, free_order=not fixed)
+                ex = sch.executor(plan, devi, stream)
+                res = torch.empty(plan.out_shape, dtype=tdt, device=dev)
+                ex.enqueue([buf.data_ptr(), zhat[other].data_ptr()], [res.data_ptr()])
+                ex.snapshot_scales(reg(LOG + child), 1)
+                kids = [g if g is not None else ZERO] + ([Z + other] if below else [])
+                add(G + child, LOG + child, kids)
+                cot[child] = (res, out_l, G + child, below)
+            del buf
+        # 3. the operands' gradients, in their own shapes and dtypes
+        for j in range(n):
+            if not need[j]:
+                continue
+            buf, lab, g, _below = cot.pop(j, (None, (), None, True))
+            shp = tuple(ops[j].shape)
+            if buf is None:
+                grads[j] = torch.zeros(shp, dtype=in_dtypes[j], device=dev)
+                continue
+            out = torch.empty(shp, dtype=in_dtypes[j], device=dev)
+            labels = sch.labels[j]
+            first = [labels.index(l) for l in labels]
+            ex_any.grad_leaf(sch.dtype, buf.data_ptr(), reg(g) if g is not None else 0, shp,
+                             _src_strides(labels, lab, sch), first,
+                             np.float32 if in_dtypes[j] == torch.float32 else np.float64, out.data_ptr())
+            grads[j] = out
+    if side is not None:
+        cur = torch.cuda.current_stream(dev)
+        cur.wait_stream(side)
+        for t in grads:
+            if t is not None:
+                t.record_stream(cur)
+    return grads
+
+
+def _src_strides(dst_labels, src_labels, sch):
+    """Element stride in a C-contiguous cotangent with axes ``src_labels`` of each label in ``dst_labels`` (0 where
+    it does not carry the label)."""
+    stride, acc = {}, 1
+    for l in reversed(tuple(src_labels)):
+        stride[l] = acc
+        acc *= sch.size[l]
+    return [stride.get(l, 0) for l in dst_labels]
+
+
+class _NullCtx:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False

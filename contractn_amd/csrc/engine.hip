@@ -38,6 +38,7 @@
 #include "kernels_sweep.h"
 #include "kernels_mfma_lat.h"
 #include "kernels_stream.h"
+#include "kernels_grad.h"
 
 namespace ctn {
 
@@ -2343,6 +2344,75 @@ int ctn_exec_step_ms(ctn_exec* exec, float* ms) {
     }
     ms[s] = (float)(acc / used);
   }
+  return CTN_OK;
+}
+
+int ctn_grad_seed(ctn_exec* exec, int dtype, const void* t_hat, const void* g_hat, const void* g_c, const double* z,
+                  const double* g_in, int64_t numel, double min_norm, void* out, double* g_out, double* scratch) {
+  if (!exec || !t_hat || !z || !out || !g_out || !scratch || numel < 1) { g_err = "invalid argument to ctn_grad_seed"; return CTN_INVALID_ARG; }
+  if (dtype != CTN_F32 && dtype != CTN_F64) { g_err = "ctn_grad_seed: dtype must be f32 or f64"; return CTN_UNSUPPORTED; }
+  Exec* E = &exec->e;
+  DeviceGuard dg(E->device);
+  HIPCHECK(dg.err);
+  const int nb = (int)std::min<int64_t>((numel + 255) / 256, kGradSeedBlocks);
+  const int dot_parts = g_hat ? nb : 0;
+  if (dtype == CTN_F32) {
+    if (g_hat) hipLaunchKernelGGL(k_grad_seed_dot<float>, dim3(nb), dim3(256), 0, E->stream, (const float*)g_hat, (const float*)t_hat, numel, scratch);
+    hipLaunchKernelGGL(k_grad_seed_apply<float>, dim3(nb), dim3(256), 0, E->stream, (const float*)g_hat, (const float*)t_hat,
+                       numel, (const float*)g_c, g_in, dot_parts, scratch, (float*)out);
+    hipLaunchKernelGGL(k_grad_seed_norm<float>, dim3(nb), dim3(256), 0, E->stream, (float*)out, numel, z, g_in, nb,
+                       (const double*)scratch, min_norm, g_out);
+  } else {
+    if (g_hat) hipLaunchKernelGGL(k_grad_seed_dot<double>, dim3(nb), dim3(256), 0, E->stream, (const double*)g_hat, (const double*)t_hat, numel, scratch);
+    hipLaunchKernelGGL(k_grad_seed_apply<double>, dim3(nb), dim3(256), 0, E->stream, (const double*)g_hat, (const double*)t_hat,
+                       numel, (const double*)g_c, g_in, dot_parts, scratch, (double*)out);
+    hipLaunchKernelGGL(k_grad_seed_norm<double>, dim3(nb), dim3(256), 0, E->stream, (double*)out, numel, z, g_in, nb,
+                       (const double*)scratch, min_norm, g_out);
+  }
+  HIPCHECK(hipGetLastError());
+  return CTN_OK;
+}
+
+int ctn_grad_leaf(ctn_exec* exec, int src_dtype, const void* src, const double* g, int ndim, const int64_t* dims,
+                  const int64_t* src_strides, const int32_t* first, int dst_dtype, void* dst) {
+  if (!exec || !src || !dst || ndim < 0 || (ndim > 0 && (!dims || !src_strides || !first))) {
+    g_err = "invalid argument to ctn_grad_leaf";
+    return CTN_INVALID_ARG;
+  }
+  if (ndim > kGradMaxDims) { g_err = "ctn_grad_leaf: more than 64 axes"; return CTN_UNSUPPORTED; }
+  if ((src_dtype != CTN_F32 && src_dtype != CTN_F64) || (dst_dtype != CTN_F32 && dst_dtype != CTN_F64)) {
+    g_err = "ctn_grad_leaf: dtypes must be f32 or f64";
+    return CTN_UNSUPPORTED;
+  }
+  GradLeafArgs a{};
+  a.ndim = ndim;
+  int64_t numel = 1;
+  for (int d = ndim - 1; d >= 0; --d) {
+    if (dims[d] < 0 || src_strides[d] < 0 || first[d] < 0 || first[d] > d || (first[d] != d && dims[first[d]] != dims[d])) {
+      g_err = "ctn_grad_leaf: inconsistent axis description";
+      return CTN_INVALID_ARG;
+    }
+    a.dims[d] = dims[d];
+    a.dst_stride[d] = numel;
+    a.src_stride[d] = first[d] == d ? src_strides[d] : 0;
+    a.first[d] = first[d];
+    numel *= dims[d];
+  }
+  a.numel = numel;
+  if (numel == 0) return CTN_OK;
+  Exec* E = &exec->e;
+  DeviceGuard dg(E->device);
+  HIPCHECK(dg.err);
+  const dim3 grid((unsigned)std::min<int64_t>((numel + 255) / 256, 4096));
+  if (src_dtype == CTN_F32 && dst_dtype == CTN_F32)
+    hipLaunchKernelGGL((k_grad_leaf<float, float>), grid, dim3(256), 0, E->stream, a, (const float*)src, g, (float*)dst);
+  else if (src_dtype == CTN_F32)
+    hipLaunchKernelGGL((k_grad_leaf<float, double>), grid, dim3(256), 0, E->stream, a, (const float*)src, g, (double*)dst);
+  else if (dst_dtype == CTN_F32)
+    hipLaunchKernelGGL((k_grad_leaf<double, float>), grid, dim3(256), 0, E->stream, a, (const double*)src, g, (float*)dst);
+  else
+    hipLaunchKernelGGL((k_grad_leaf<double, double>), grid, dim3(256), 0, E->stream, a, (const double*)src, g, (double*)dst);
+  HIPCHECK(hipGetLastError());
   return CTN_OK;
 }
 

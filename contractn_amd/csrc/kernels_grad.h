@@ -1,0 +1,110 @@
+// kernels_grad.h - reverse mode of the stabilised contraction ("Autograd"): the split-format seed and the
+// leaf write.  The cotangent contractions themselves are ordinary one-step plans run on the forward kernels.
+// Part of the gfx950 contraction engine (see engine.hip for the overview).
+#pragma once
+#include "kernel_args.h"
+
+namespace ctn {
+
+// ---------------------------------------------------------------------------
+// k_grad_seed_*: the cotangent of the plain value Z of a rescaled step from those of its split outputs
+// (Z_hat = Z / mean|Z|, z = log mean|Z|), everything in split form G = G_hat e^g:
+//     G_Z = e^{g - z} [G_hat - (<G_hat, Z_hat> - G_c e^{-g}) sign(Z_hat) / N]
+// then re-stabilised: out = bracket / mean|bracket|, g_out = g - z + log mean|bracket| (when sum|bracket| > min_norm).
+// Three launches of kGradSeedBlocks workgroups at most: the partial dot products, the bracket with its partial
+// abs-sums, the division.  Every workgroup owns a fixed set of elements and every sum of partials runs in one fixed
+// order, so the result is bit-reproducible.  g_hat == nullptr: G_hat = 0; g_c == nullptr: G_c = 0; g_in == nullptr:
+// g = 0.  scratch: 2 * kGradSeedBlocks doubles.
+// ---------------------------------------------------------------------------
+constexpr int kGradSeedBlocks = 256;
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_dot(const T* __restrict__ g_hat, const T* __restrict__ t_hat,
+                                                       int64_t n, double* __restrict__ scratch) {
+  __shared__ double red[4];
+  double v = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    v += (double)g_hat[i] * (double)t_hat[i];
+  const double tot = block_sum(v, red);
+  if (threadIdx.x == 0) scratch[blockIdx.x] = tot;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_apply(const T* __restrict__ g_hat, const T* __restrict__ t_hat,
+                                                         int64_t n, const T* __restrict__ g_c,
+                                                         const double* __restrict__ g_in, int dot_parts,
+                                                         double* __restrict__ scratch, T* __restrict__ out) {
+  __shared__ double red[4];
+  double dot = 0.0;
+  for (int j = 0; j < dot_parts; ++j) dot += scratch[j];          // same order in every thread of every workgroup
+  const double gc = g_c ? (double)g_c[0] : 0.0;
+  const double g = g_in ? g_in[0] : 0.0;
+  const double alpha = (dot - (gc == 0.0 ? 0.0 : gc * exp(-g))) / (double)n;
+  double absv = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const double t = (double)t_hat[i];
+    const double sg = t > 0.0 ? 1.0 : (t < 0.0 ? -1.0 : 0.0);     // sign(0) = 0, as torch.sign
+    const T b = (T)((g_hat ? (double)g_hat[i] : 0.0) - alpha * sg);
+    out[i] = b;
+    absv += fabs((double)b);
+  }
+  const double tot = block_sum(absv, red);
+  if (threadIdx.x == 0) scratch[kGradSeedBlocks + blockIdx.x] = tot;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_norm(T* __restrict__ out, int64_t n, const double* __restrict__ z,
+                                                        const double* __restrict__ g_in, int parts,
+                                                        const double* __restrict__ scratch, double min_norm,
+                                                        double* __restrict__ g_out) {
+  double norm = 0.0;
+  for (int j = 0; j < parts; ++j) norm += scratch[kGradSeedBlocks + j];
+  const bool resc = norm > min_norm;
+  const double mean = norm / (double)n;
+  if (resc)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+      out[i] = (T)((double)out[i] / mean);
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    g_out[0] = (g_in ? g_in[0] : 0.0) - z[0] + (resc ? log(mean) : 0.0);
+}
+
+// ---------------------------------------------------------------------------
+// k_grad_leaf: one operand's gradient, written destination-driven in the operand's own shape (C-contiguous) and
+// dtype, dst[i] = src[sum_d c_d src_stride[d]] * e^{g}.  The cotangent contraction left its result in whatever axis
+// order its plan chose: src_stride[d] is the stride of axis d's label in that result, 0 for a label the result does
+// not carry (summed inside the operand alone: the gradient is constant along it).  A label repeated in the operand
+// (a trace, `aa->`) is read at its first axis (first[d] == d) and the element is 0 where the repeats disagree.  An
+// exact zero stays 0 whatever e^{g}; anything else overflows to inf as the reference's own graph does.
+// ---------------------------------------------------------------------------
+constexpr int kGradMaxDims = 64;
+struct GradLeafArgs {
+  int64_t numel;
+  int32_t ndim, pad;
+  int64_t dims[kGradMaxDims];
+  int64_t dst_stride[kGradMaxDims];
+  int64_t src_stride[kGradMaxDims];
+  int32_t first[kGradMaxDims];
+};
+
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void k_grad_leaf(GradLeafArgs a, const TS* __restrict__ src,
+                                                   const double* __restrict__ g, TD* __restrict__ dst) {
+  const double m = g ? exp(g[0]) : 1.0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.numel; i += (int64_t)gridDim.x * 256) {
+    int64_t off = 0;
+    bool on = true;
+    for (int d = 0; d < a.ndim; ++d) {
+      const int64_t c = (i / a.dst_stride[d]) % a.dims[d];
+      const int f = a.first[d];
+      if (f != d) {
+        if (c != (i / a.dst_stride[f]) % a.dims[f]) { on = false; break; }
+      } else {
+        off += c * a.src_stride[d];
+      }
+    }
+    const double v = on ? (double)src[off] : 0.0;
+    dst[i] = (TD)(v == 0.0 ? 0.0 : v * m);
+  }
+}
+
+}  // namespace ctn

@@ -359,7 +359,7 @@ def _core_contract(operands, contract_list, backend="numpy", _plain=False, **ein
         return _core_contract_complex(operands, contract_list, shapes, dtype, backend)
     plan = _native_plan(contract_list, shapes, dtype.name)
     if backend == "torch":
-        return _run_torch(plan, operands, dtype, plain=_plain)
+        return _run_torch(plan, operands, dtype, plain=_plain, contract_list=contract_list)
     with _locked_executor(plan, 1) as ex:
         outs, _dev_log, resc = ex.run_host([operands])
     log_scale = accumulate_log_scale(resc[0], dtype)
@@ -513,22 +513,36 @@ def _core_contract_complex(operands, contract_list, shapes, dtype, backend):
     return res, log_scale
 
 
-def _run_torch(plan, operands, dtype, plain=False):
+def _run_torch(plan, operands, dtype, plain=False, contract_list=None):
     import torch
 
     tdt = torch.float32 if dtype == np.float32 else torch.float64
     if torch.is_grad_enabled() and any(o.requires_grad for o in operands):
-        # the reference's torch backend is differentiable (einsum.py:9-21); this engine writes into a fresh
-        # buffer outside autograd, so a training loop would silently get no gradients - refuse instead
+        # the reference's torch backend is differentiable (einsum.py:9-21): on the GPU the contraction is a
+        # torch.autograd.Function (autograd.py); elsewhere this engine writes into a fresh buffer outside autograd,
+        # so a training loop would silently get no gradients - refuse instead
+        if contract_list is not None and all(o.is_cuda for o in operands):
+            from . import autograd
+
+            return autograd.contract_with_grad(plan, operands, dtype, plain, contract_list)
         raise NotImplementedError(
-            "the HIP engine does not build an autograd graph: detach() the operands or contract under "
-            "torch.no_grad()")
+            "the HIP engine builds an autograd graph only for operands on the GPU: move them to the device, "
+            "detach() them or contract under torch.no_grad()")
     if not all(o.is_cuda for o in operands):
         host = [o.detach().cpu().numpy() for o in operands]
         with _locked_executor(plan, 1) as ex:
             outs, _dev_log, resc = ex.run_host([host])
         log_scale = accumulate_log_scale(resc[0], dtype, register_dtype=dtype)
         return torch.from_numpy(np.array(outs[0])), torch.tensor(float(log_scale), dtype=tdt)   # (a closed network: 0-d)
+    out, log_scale, _resc, _ops = _run_torch_device(plan, operands, dtype, plain)
+    return out, log_scale
+
+
+def _run_torch_device(plan, operands, dtype, plain=False):
+    """`_run_torch` on device operands: ``(result, register or None, per-step rescales, operands as run)``."""
+    import torch
+
+    tdt = torch.float32 if dtype == np.float32 else torch.float64
     dev = operands[0].device
     ops = [o.to(device=dev, dtype=tdt).contiguous() for o in operands]
     # views into a larger storage may start at an odd offset: vector loads need 16-byte alignment
@@ -557,8 +571,8 @@ def _run_torch(plan, operands, dtype, plain=False):
             if plain:
                 ex.set_finish_mode(0)
     if plain:
-        return out, None
-    return out, torch.tensor(float(log_scale), dtype=tdt, device=dev)
+        return out, None, resc[0], ops
+    return out, torch.tensor(float(log_scale), dtype=tdt, device=dev), resc[0], ops
 
 
 # ---------------------------------------------------------------------------

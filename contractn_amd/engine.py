@@ -41,7 +41,10 @@ ABI_SYMBOLS = (
     "ctn_exec_snapshot_scales", "ctn_exec_scales_suspect", "ctn_exec_combine_split",
     "ctn_exec_add_scales", "ctn_exec_merge_scales", "ctn_exec_report_suspect",
     "ctn_exec_set_finish_mode", "ctn_exec_finish",
+    "ctn_grad_seed", "ctn_grad_leaf",
 )
+GRAD_SCRATCH = 512          # doubles of scratch ctn_grad_seed needs (CTN_GRAD_SCRATCH)
+GRAD_MAX_DIMS = 64          # axes of an operand ctn_grad_leaf writes (CTN_GRAD_MAX_DIMS)
 
 
 class PlanDesc(C.Structure):
@@ -165,6 +168,9 @@ def load_library():
         "ctn_exec_finish": (i32, [vp, C.POINTER(C.c_double)]),
         "ctn_exec_add_scales": (i32, [vp, vp, vp, i32, i32, C.POINTER(vp), C.POINTER(vp)]),
         "ctn_exec_merge_scales": (i32, [vp, i32, vp, i64, i64, vp, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "ctn_grad_seed": (i32, [vp, i32, vp, vp, vp, vp, vp, i64, f64, vp, vp, vp]),
+        "ctn_grad_leaf": (i32, [vp, i32, vp, vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int32), i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -494,6 +500,26 @@ class Executor:
         _check(self._lib.ctn_exec_merge_scales(self._h, CTN_F32 if dt == np.float32 else CTN_F64, C.c_void_p(buf_ptr),
                                                int(stride), int(numel), C.c_void_p(scales_ptr), int(n), len(ext),
                                                _ptr(ext, C.c_int32), _ptr(mrg, C.c_int32)))
+
+    # -- reverse mode (include/ctn_abi.h, ctn_grad_*): kernels on this executor's stream ----------------------
+    def grad_seed(self, dtype, t_hat_ptr, g_hat_ptr, g_c_ptr, z_ptr, g_in_ptr, numel, min_norm, out_ptr, g_out_ptr,
+                  scratch_ptr):
+        """Enqueue the split-format seed: ``out * e^{g_out}`` = cotangent of the plain value behind ``(t_hat, z)``
+        (device pointers; ``g_hat_ptr`` / ``g_c_ptr`` / ``g_in_ptr`` may be 0 = a zero cotangent / register)."""
+        code = CTN_F32 if np.dtype(dtype) == np.float32 else CTN_F64
+        _check(self._lib.ctn_grad_seed(self._h, code, C.c_void_p(t_hat_ptr), C.c_void_p(g_hat_ptr or None),
+                                       C.c_void_p(g_c_ptr or None), C.c_void_p(z_ptr), C.c_void_p(g_in_ptr or None),
+                                       int(numel), float(min_norm), C.c_void_p(out_ptr), C.c_void_p(g_out_ptr),
+                                       C.c_void_p(scratch_ptr)))
+
+    def grad_leaf(self, src_dtype, src_ptr, g_ptr, dims, src_strides, first, dst_dtype, dst_ptr):
+        """Enqueue an operand's gradient ``dst`` (shape ``dims``, C-contiguous) gathered from the cotangent ``src``
+        times ``e^{*g}`` (include/ctn_abi.h, ctn_grad_leaf)."""
+        d, st, fi = _i64(dims), _i64(src_strides), _i32(first)
+        _check(self._lib.ctn_grad_leaf(self._h, CTN_F32 if np.dtype(src_dtype) == np.float32 else CTN_F64,
+                                       C.c_void_p(src_ptr), C.c_void_p(g_ptr or None), len(d), _ptr(d, C.c_int64),
+                                       _ptr(st, C.c_int64), _ptr(fi, C.c_int32),
+                                       CTN_F32 if np.dtype(dst_dtype) == np.float32 else CTN_F64, C.c_void_p(dst_ptr)))
 
     def set_timing(self, slots):
         """Bracket every step of the next ``slots`` enqueues with HIP events (0 = off)."""

@@ -277,6 +277,32 @@ int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t*
 int ctn_exec_set_timing(ctn_exec* exec, int slots);
 int ctn_exec_step_ms(ctn_exec* exec, float* ms);
 
+/*
+ * Reverse mode of the stabilised contraction ("Autograd").  Cotangents are kept in split form G_hat e^g
+ * with g a float64 device register; the cotangent contractions themselves are ordinary one-step plans.  Both run on
+ * the stream of `exec` (any executor of the caller's device and stream); all pointers are device pointers.
+ *
+ * ctn_grad_seed: the cotangent of the plain value Z of a rescaled result from those of its split outputs
+ *   (t_hat = Z / mean|Z|, its register z; incoming cotangents G_hat e^g of t_hat and G_c of z):
+ *     G_Z = e^{g - z} [G_hat - (<G_hat, t_hat> - G_c e^{-g}) sign(t_hat) / N]   (sign(0) = 0),
+ *   written as out e^{g_out}: the bracket divided by its mean magnitude when its abs-sum exceeds min_norm,
+ *   g_out = g - z + log(that mean).
+ *   t_hat, g_hat, out: numel elements of `dtype`; g_c: one element of `dtype`; z, g_in, g_out: one double each.
+ *   g_hat, g_c, g_in may be NULL (= 0).  Both sums run in a fixed order (bit-reproducible).
+ *   scratch: CTN_GRAD_SCRATCH doubles.
+ * ctn_grad_leaf: an operand's gradient in its own shape dims[ndim] (C-contiguous, dst_dtype):
+ *   dst[c] = src[sum_d c_d src_strides[d]] * e^{*g}  (g may be NULL = 0), where src_strides[d] is the element stride
+ *   of axis d's label in the cotangent `src` (0 for a label it does not carry: constant along it) and first[d] the
+ *   first axis with the same label (d itself if none before): where a repeated label's coordinates disagree the
+ *   element is 0.  ndim <= CTN_GRAD_MAX_DIMS.  An exact zero stays 0; overflow gives inf.
+ */
+#define CTN_GRAD_SCRATCH 512
+#define CTN_GRAD_MAX_DIMS 64
+int ctn_grad_seed(ctn_exec* exec, int dtype, const void* t_hat, const void* g_hat, const void* g_c, const double* z,
+                  const double* g_in, int64_t numel, double min_norm, void* out, double* g_out, double* scratch);
+int ctn_grad_leaf(ctn_exec* exec, int src_dtype, const void* src, const double* g, int ndim, const int64_t* dims,
+                  const int64_t* src_strides, const int32_t* first, int dst_dtype, void* dst);
+
 #ifdef __cplusplus
 }
 #endif

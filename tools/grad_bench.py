@@ -1,0 +1,101 @@
+"""Backward cost of contract() on device tensors (contractn_amd/autograd.py), one MI355X.
+
+    python tools/grad_bench.py [--reps 5] [--warmup 2]
+
+Per network: the no-grad forward, then forward + backward of a loss on ``(T_hat, c)``, both timed with torch events on
+the current stream (median of ``--reps``).  The backward's algorithmic work is taken as twice the forward plan's flops
+(each pairwise step has two cotangent contractions of its own GEMM shape) plus one recomputed forward, and reported as
+TFLOP/s against the MFMA peak of the dtype.  Networks:
+
+* ``mps100_D256``: the 100-site D = 256 MPS overlap (fp32), one network;
+* ``mps100_D64_classifier``: a 100-site D = 64 batched-MPS classifier training step, B = 256 inputs (fp32);
+* ``readme_3x3_chain``: the README's 1000-matrix 3 x 3 chain (fp64, split format; its plain value is inf).
+One JSON line per network.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_TFLOPS = {"float32": 157.3, "float64": 78.6}     # MI355X dense MFMA peaks (fp32, fp64)
+
+
+def timed(torch, fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts))
+
+
+def networks(torch):
+    from contractn_amd import TN
+    from contractn_amd.paths import ssa_to_linear
+    from tests import networks as nets
+    from tests.helpers import load_golden
+
+    tn, ssa = nets.mps_overlap(TN, 100, 256, 4, dtype=np.float32, seed=3)
+    yield ("mps100_D256", tn.einsum_str, [np.asarray(p) for p in tn.params], ssa_to_linear(ssa, 200),
+           [True] * len(tn.params))
+    tn, inputs = nets.batched_mps(TN, 100, 64, 4, 256, dtype=np.float32, seed=4)
+    ops = [np.asarray(p) for p in tn.params] + [np.asarray(x) for x in inputs]
+    yield ("mps100_D64_classifier", tn.einsum_str, ops, ssa_to_linear(nets.batched_mps_path(100), 200),
+           [True] * 100 + [False] * 100)
+    g = load_golden("readme_chain1000")
+    yield ("readme_3x3_chain", g["einsum_str"], [np.asarray(a, dtype=np.float64) for a in g["operands"]], g["path"],
+           [True] * len(g["operands"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    import torch
+
+    from contractn_amd import einsum as E
+
+    for name, einstr, arrays, path, trainable in networks(torch):
+        ops = [torch.tensor(a, device="cuda") for a in arrays]
+        dt = str(arrays[0].dtype)
+        shapes = tuple(tuple(a.shape) for a in arrays)
+        clist = E._contract_path(einstr, shapes, optimize=tuple(tuple(p) for p in path), memory_limit=None,
+                                 use_blas=True)
+        flops = E._native_plan(clist, shapes, dt).flops
+
+        def fwd():
+            with torch.no_grad():
+                E.contract(einstr, *ops, optimize=path, split_format=True)
+
+        params = [o.clone().requires_grad_(t) for o, t in zip(ops, trainable)]
+        leaves = [p for p in params if p.requires_grad]
+
+        def fwd_bwd():
+            t_hat, c = E.contract(einstr, *params, optimize=path, split_format=True)
+            loss = t_hat.square().sum() + c
+            torch.autograd.grad(loss, leaves)
+
+        t_f = timed(torch, fwd, args.reps, args.warmup)
+        t_fb = timed(torch, fwd_bwd, args.reps, args.warmup)
+        t_b = max(t_fb - t_f, 1e-6)
+        bwd_flops = 3.0 * flops
+        tflops = bwd_flops / (t_b * 1e-3) / 1e12
+        print(json.dumps({"network": name, "dtype": dt, "forward_ms": round(t_f, 3), "fwd_bwd_ms": round(t_fb, 3),
+                          "ratio": round(t_fb / t_f, 2), "backward_tflops": round(tflops, 2),
+                          "of_peak": round(tflops / PEAK_TFLOPS[dt], 3)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
