@@ -142,6 +142,41 @@ class BackwardSchedule:
         back = {v: k for k, v in m.items()}
         return hit, tuple(back[l] for l in hit.out_labels)
 
+    def recompute_plan(self, k):
+        """The one-step plan that recomputes forward step ``k`` (Z_hat_k and z_k)."""
+        a, b, out = self.steps[k]
+        return self.plan([self.labels[a]] + ([self.labels[b]] if b >= 0 else []), out, einsum.MIN_NORM)[0]
+
+    def walk(self, need, frontier):
+        """The reverse walk as host structure, root down: per step ``k`` that needs a cotangent, ``(k, moves)`` with one
+        move ``(child, other, plan, out_labels, below)`` per child that needs one.  ``plan`` is the cotangent contraction
+        of the step's cotangent with sibling ``other`` (None for a unary step, whose cotangent passes down as it is),
+        ``out_labels`` the labels of what the child receives, ``below``: the step's cotangent is below the frontier
+        (after the split-format seed at a frontier step), so ``z`` of the sibling enters the child's ``g``."""
+        n = self.n_inputs
+        state = {self.root: (self.labels[self.root], not self.split_format)}
+        for k in reversed(range(self.n_steps)):
+            i = n + k
+            if not need[i] or i not in state:
+                continue
+            lab, below = state.pop(i)
+            if k in frontier:
+                lab, below = self.labels[i], True
+            a, b, _out = self.steps[k]
+            moves = []
+            for child, other in ((a, b), (b, a)):
+                if child < 0 or not need[child]:
+                    continue
+                if other < 0:
+                    moves.append((child, other, None, lab, below))
+                else:
+                    fixed = self.split_format and not below and child >= n and (child - n) in frontier
+                    plan, out_l = self.plan([lab, self.labels[other]], self.cot_labels[child], GRAD_MIN_NORM,
+                                            free_order=not fixed)
+                    moves.append((child, other, plan, out_l, below))
+                state[child] = (moves[-1][3], below)
+            yield k, moves
+
     def executor(self, plan, device, stream):
         key = (id(plan), device, stream, threading.get_ident())
         with self._lock:
@@ -303,8 +338,7 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
         ex_any = None
         for k in range(last):
             a, b, out = sch.steps[k]
-            ins = [sch.labels[a]] + ([sch.labels[b]] if b >= 0 else [])
-            plan, _ = sch.plan(ins, out, einsum.MIN_NORM)
+            plan = sch.recompute_plan(k)
             ex = ex_any = sch.executor(plan, devi, stream)
             buf = torch.empty(plan.out_shape, dtype=tdt, device=dev)
             ex.enqueue([zhat[a].data_ptr()] + ([zhat[b].data_ptr()] if b >= 0 else []), [buf.data_ptr()])
@@ -312,9 +346,7 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
             zhat[n + k] = buf
             add(Z + n + k, LOG + n + k, [Z + a] + ([Z + b] if b >= 0 else []))
         if ex_any is None:          # a one-step plain contraction: any executor of the stream runs the bookkeeping
-            a, b, out = sch.steps[0]
-            ins = [sch.labels[a]] + ([sch.labels[b]] if b >= 0 else [])
-            ex_any = sch.executor(sch.plan(ins, out, einsum.MIN_NORM)[0], devi, stream)
+            ex_any = sch.executor(sch.recompute_plan(0), devi, stream)
         if flags_host is not None:
             (side if side is not None else torch.cuda.current_stream(dev)).synchronize()   # the one host wait
             rescaled = [bool(v > 0) for v in flags_host.tolist()]
@@ -323,8 +355,8 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
         frontier = set(sch.frontier(rescaled))
         scratch = torch.empty(engine.GRAD_SCRATCH, dtype=torch.float64, device=dev) if frontier else None
 
-        # 2. the reverse walk: cot[id] = (buffer or None, labels, g register or None, below the frontier?)
-        cot = {sch.root: (g_t, sch.labels[sch.root], None, not sch.split_format)}
+        # 2. the reverse walk (sch.walk): cot[id] = (buffer or None, its labels, g register or None)
+        cot = {sch.root: (g_t, sch.labels[sch.root], None)}
         grads = [None] * n
 
         def expand(buf, labels, full):
@@ -337,11 +369,9 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
                              list(range(len(full))), sch.dtype, dst.data_ptr())
             return dst
 
-        for k in reversed(range(S)):
+        for k, moves in sch.walk(need, frontier):
             i = n + k
-            if not need[i] or i not in cot:
-                continue
-            buf, lab, g, below = cot.pop(i)
+            buf, lab, g = cot.pop(i)
             if k in frontier:
                 full = sch.labels[i]
                 gh = expand(buf, lab, full)
@@ -350,33 +380,27 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
                                  g_c.data_ptr() if g_c is not None else 0, reg(Z + i),
                                  reg(g) if g is not None else 0, out.numel(), GRAD_MIN_NORM, out.data_ptr(),
                                  reg(SEED + i), scratch.data_ptr())
-                buf, lab, g, below = out, full, SEED + i, True
-            a, b, _out = sch.steps[k]
-            for child, other in ((a, b), (b, a)):
-                if child < 0 or not need[child]:
-                    continue
+                buf, g = out, SEED + i
+            for child, other, plan, out_l, below in moves:
                 if buf is None:
-                    cot[child] = (None, (), None, below)
+                    cot[child] = (None, (), None)
                     continue
-                if other < 0:                       # unary step: the cotangent passes down as it is
-                    cot[child] = (buf, lab, g, below)
+                if plan is None:                    # unary step: the cotangent passes down as it is
+                    cot[child] = (buf, out_l, g)
                     continue
-                gl = sch.cot_labels[child]
-                fixed = sch.split_format and not below and child >= n and (child - n) in frontier
-                plan, out_l = sch.plan([lab, sch.labels[other]], gl, GRAD_MIN_NORM, free_order=not fixed)
                 ex = sch.executor(plan, devi, stream)
                 res = torch.empty(plan.out_shape, dtype=tdt, device=dev)
                 ex.enqueue([buf.data_ptr(), zhat[other].data_ptr()], [res.data_ptr()])
                 ex.snapshot_scales(reg(LOG + child), 1)
                 kids = [g if g is not None else ZERO] + ([Z + other] if below else [])
                 add(G + child, LOG + child, kids)
-                cot[child] = (res, out_l, G + child, below)
+                cot[child] = (res, out_l, G + child)
             del buf
         # 3. the operands' gradients, in their own shapes and dtypes
         for j in range(n):
             if not need[j]:
                 continue
-            buf, lab, g, _below = cot.pop(j, (None, (), None, True))
+            buf, lab, g = cot.pop(j, (None, (), None))
             shp = tuple(ops[j].shape)
             if buf is None:
                 grads[j] = torch.zeros(shp, dtype=in_dtypes[j], device=dev)

@@ -1689,8 +1689,11 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   HIPCHECK_X(hipMalloc((void**)&E.d_ptrs, (size_t)replicas * E.n_tensors * sizeof(void*)));
   {
     size_t slab_elems = 0;   // split-K scratch: S slabs shaped like the step's output, per replica
-    auto splits_of = [&](const Step& st) {
-      if (P.dtype == CTN_F32)
+    // the splits the launcher will take, in its order: the large-tile split-K only on a step with a consumer (the
+    // final step goes on to the latency form, whose S can exceed the 16 slabs of the large-tile one)
+    auto splits_of = [&](int s) {
+      const Step& st = P.steps[s];
+      if (P.dtype == CTN_F32 && s + 1 < P.n_steps)
         if (const int S = g_splitk(st, replicas, E.n_cu, E.mfma_g, E.sw, st.cvec)) return S;
       if (lat_form(st, replicas, E.n_cu, P.dtype, E.sw)) return 0;
       if (const int S = splitk_splits(st, replicas, E.n_cu, P.dtype, E.sw)) return S;
@@ -1698,15 +1701,15 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       if (const int S = stream_splits(st, replicas, E.n_cu)) return S;
       return rowdot_splits(st, replicas, E.n_cu);
     };
-    for (const Step& st : P.steps)
-      if (const int S = splits_of(st))
-        slab_elems = std::max(slab_elems, (size_t)S * (size_t)P.tensors[st.out].numel * (size_t)replicas);
+    for (int s = 0; s < P.n_steps; ++s)
+      if (const int S = splits_of(s))
+        slab_elems = std::max(slab_elems, (size_t)S * (size_t)P.tensors[P.steps[s].out].numel * (size_t)replicas);
     if (slab_elems) HIPCHECK_X(hipMalloc((void**)&E.d_slab, slab_elems * (P.dtype == CTN_F64 ? 8 : 4)));
     size_t fold_elems = 0;   // a step with more than 16 slabs folds them 16 to 1 into this buffer and back
-    for (const Step& st : P.steps)
-      if (const int S = splits_of(st))
+    for (int s = 0; s < P.n_steps; ++s)
+      if (const int S = splits_of(s))
         if (S > 16)
-          fold_elems = std::max(fold_elems, (size_t)((S + 15) / 16) * (size_t)P.tensors[st.out].numel * (size_t)replicas);
+          fold_elems = std::max(fold_elems, (size_t)((S + 15) / 16) * (size_t)P.tensors[P.steps[s].out].numel * (size_t)replicas);
     if (fold_elems) HIPCHECK_X(hipMalloc((void**)&E.d_slab2, fold_elems * (P.dtype == CTN_F64 ? 8 : 4)));
   }
   // partial counts: plan value, one per tile in the latency form, and the split-K reduce pass spreads over up to

@@ -248,7 +248,11 @@ class _locked_executor:
 
 
 def clear_caches():
-    """Drop every cached executor (device memory), native plan and contraction path."""
+    """Drop every cached executor (device memory), native plan and contraction path - the backward's schedules and
+    their executors (autograd.py) included."""
+    from . import autograd
+
+    autograd.clear_caches()
     with _EXECUTOR_LRU_LOCK:
         dropped = list(_EXECUTOR_LRU.values())
         _EXECUTOR_LRU.clear()

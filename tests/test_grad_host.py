@@ -9,6 +9,7 @@ import pytest
 from contractn_amd import autograd as AG
 from contractn_amd import einsum as E
 from contractn_amd import engine
+from tests import grad_cases as GC
 from tests.grad_fixtures import GRAD_DIR, load_grad_fixture
 from tests.helpers import ROOT
 
@@ -126,3 +127,73 @@ def test_fixtures_agree_with_plain_torch_autograd(name):
         g = torch.zeros(ref.shape, dtype=torch.float64) if g is None else g
         err = float((g - torch.tensor(ref, dtype=torch.float64)).norm()) / max(float(np.linalg.norm(ref)), 1e-300)
         assert err <= (1e-10 if fx["dtype"] == "float64" else 1e-4), name
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the networks of tests/test_gpu_grad_kernels.py (tests/grad_cases.py): the one-step plans their backward runs reach the
+# forms that file claims to cover - a planner change that moves them off is noticed here
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("name", sorted(GC.FORMS))
+def test_gpu_grad_cases_reach_their_forms(name, split):
+    for dtype in ("float32", "float64"):
+        assert not GC.missing_forms(name, dtype, split), (name, dtype, split)
+
+
+def test_gpu_grad_cases_cover_the_backward_kernels():
+    """Across the GPU file's networks the cotangent steps alone reach every form the backward adds to the forward."""
+    cot = []
+    for name in GC.GRAD_KERNEL_NETWORKS:
+        for dtype in ("float32", "float64"):
+            for split in (True, False):
+                cot += GC.network_forms(name, dtype, split)[1]
+    for what, pred in (("256-row, modes (2,2)", lambda i: GC.large(i, 2, 2)),
+                       ("256-row, modes (1,2)", lambda i: GC.large(i, 1, 2)),
+                       ("kernel 3", lambda i: i["kernel"] == 3),
+                       ("kernel 4", lambda i: i["kernel"] == 4),
+                       ("a ragged M, N or K", GC.ragged),
+                       ("a large-tile K >= 1024", lambda i: i["tile_m"] == 256 and i["k"] >= 1024)):
+        assert any(pred(i) for i in cot), what
+
+
+def test_forms_notice_a_shrunk_network(monkeypatch):
+    """The form checks fail when a case no longer reaches its kernel: the MPS overlap at D = 64 has no 256-row step."""
+    monkeypatch.setitem(GC.GRAD_KERNEL_NETWORKS, "mps6_D256", lambda: GC.mps_overlap_case([64] * 5, 4))
+    assert "256-row, modes (2,2)" in GC.missing_forms("mps6_D256", "float32", True)
+
+
+def test_walk_matches_the_schedule_structure():
+    """BackwardSchedule.walk: every needed id gets its cotangent once, with the structural labels (up to order)."""
+    einstr, shapes, path = GC.GRAD_KERNEL_NETWORKS["mps8_uneven"]()
+    for split in (True, False):
+        sch = GC.schedule_of(einstr, shapes, path, "float32", split)
+        need = sch.needs([True] * sch.n_inputs)
+        seen = []
+        for _k, moves in sch.walk(need, set(sch.frontier([True] * sch.n_steps))):
+            for child, _other, plan, out_l, _below in moves:
+                seen.append(child)
+                assert sorted(out_l) == sorted(sch.cot_labels[child]) and plan is not None
+                assert tuple(plan.out_shape) == sch.shape_of(out_l)
+        assert sorted(seen) == list(range(sch.root))
+
+
+def test_the_2p31_gradient_is_one_streaming_outer_product():
+    """`ab,b->a` with A of 2^16 x (2^15 + 64): A's cotangent is w (x) y, one step past 2^31 outputs."""
+    rec, cot = GC.backward_step_infos("ab,b->a", [(1 << 16, (1 << 15) + 64), ((1 << 15) + 64,)], [(0, 1)], "float32",
+                                      False, needs=[True, False])
+    assert len(cot) == 1 and cot[0]["out_numel"] == (1 << 16) * ((1 << 15) + 64) and cot[0]["k"] == 1
+
+
+def test_clear_caches_drops_the_backward_schedules():
+    """contractn_amd.clear_caches() also closes the executors of the backward (autograd._SCHEDULES): a switch set
+    before it (CTN_MFMA_G, CTN_SPLITK, ...) reaches the next backward."""
+    import contractn_amd
+
+    shapes = ((3, 4), (4, 5))
+    clist = E._contract_path("ab,bc->ac", shapes, optimize="auto", memory_limit=None, use_blas=True)
+    sch = AG.backward_schedule(clist, shapes, "float32", True)
+    closed = []
+    sch.close = lambda: closed.append(sch)
+    assert AG._SCHEDULES
+    contractn_amd.clear_caches()
+    assert not AG._SCHEDULES and closed == [sch]
