@@ -48,11 +48,23 @@ class BackwardSchedule:
     One-step native plans are built on first use and shared between steps of equal structure."""
 
     def __init__(self, contract_list, shapes, dtype_name, split_format):
-        self.shapes = tuple(tuple(int(d) for d in s) for s in shapes)
+        shapes = tuple(tuple(int(d) for d in s) for s in shapes)
+        in_labels, steps = einsum.lower_contraction_list(len(shapes), contract_list, shapes)
+        self._build(in_labels, steps, shapes, dtype_name, split_format)
+
+    @classmethod
+    def from_ssa(cls, in_labels, steps, shapes, dtype_name, split_format):
+        """The schedule of a path already in SSA form (``in_labels``, ``steps`` as `einsum.lower_contraction_list` gives
+        them): the real plan of a complex network (`einsum._complex_plan_cached`) is built that way."""
+        self = cls.__new__(cls)
+        self._build(in_labels, steps, tuple(tuple(int(d) for d in s) for s in shapes), dtype_name, split_format)
+        return self
+
+    def _build(self, in_labels, steps, shapes, dtype_name, split_format):
+        self.shapes = shapes
         self.dtype = np.dtype(dtype_name)
         self.split_format = bool(split_format)
         n = self.n_inputs = len(self.shapes)
-        in_labels, steps = einsum.lower_contraction_list(n, contract_list, self.shapes)
         self.steps = [(int(a), int(b), tuple(out)) for a, b, out in steps]
         self.n_steps = len(self.steps)
         self.root = n + self.n_steps - 1
@@ -201,13 +213,25 @@ _SCHEDULES_LOCK = threading.Lock()
 def backward_schedule(contract_list, shapes, dtype_name, split_format):
     """Cached `BackwardSchedule` (like `einsum._native_plan`)."""
     key = (contract_list, tuple(tuple(int(d) for d in s) for s in shapes), str(dtype_name), bool(split_format))
+    return _cached_schedule(key, lambda: BackwardSchedule(contract_list, key[1], key[2], key[3]))
+
+
+def ssa_backward_schedule(ssa, shapes, dtype_name, split_format):
+    """Cached `BackwardSchedule.from_ssa` of ``ssa = (in_labels, steps)``."""
+    in_labels, steps = ssa
+    key = ("ssa", in_labels, steps, tuple(tuple(int(d) for d in s) for s in shapes), str(dtype_name),
+           bool(split_format))
+    return _cached_schedule(key, lambda: BackwardSchedule.from_ssa(in_labels, steps, key[3], key[4], key[5]))
+
+
+def _cached_schedule(key, make):
     evicted = []
     with _SCHEDULES_LOCK:
         sch = _SCHEDULES.get(key)
         if sch is not None:
             _SCHEDULES.move_to_end(key)
             return sch
-        sch = BackwardSchedule(contract_list, key[1], key[2], key[3])
+        sch = make()
         _SCHEDULES[key] = sch
         while len(_SCHEDULES) > MAX_CACHED_SCHEDULES:
             evicted.append(_SCHEDULES.popitem(last=False)[1])
@@ -243,15 +267,19 @@ def _stream_for(torch, dev):
 # ---------------------------------------------------------------------------
 # the autograd Function
 # ---------------------------------------------------------------------------
-def contract_with_grad(plan, operands, dtype, plain, contract_list):
-    """`einsum._run_torch` for device operands of which some require grad: same values, plus a graph."""
+def contract_with_grad(plan, operands, dtype, plain, contract_list, ssa=None, info=None):
+    """`einsum._run_torch` for device operands of which some require grad: same values, plus a graph.
+
+    ``ssa``: ``(in_labels, steps)`` of a plan that is not ``contract_list`` lowered as it stands - the real plan of a
+    complex network (`einsum._complex_plan_cached`) - for the backward schedule.  ``info``: a dict that receives
+    ``root_rescaled``, whether the forward rescaled its root."""
     import torch
 
     for o in operands:
         if o.requires_grad and o.dtype not in (torch.float32, torch.float64):
             raise NotImplementedError(f"autograd of contract(): operands of {o.dtype} are not supported")
     fn = _function(torch)
-    res = fn.apply((plan, np.dtype(dtype), bool(plain), contract_list), *operands)
+    res = fn.apply((plan, np.dtype(dtype), bool(plain), contract_list, ssa, info), *operands)
     if plain:
         return res, None
     return res
@@ -268,13 +296,15 @@ def _function(torch):
     class ContractFunction(torch.autograd.Function):
         @staticmethod
         def forward(ctx, meta, *operands):
-            plan, dtype, plain, contract_list = meta
+            plan, dtype, plain, contract_list, _ssa, info = meta
             out, log_scale, resc, ops = einsum._run_torch_device(plan, operands, dtype, plain)
             ctx.set_materialize_grads(False)
             ctx.meta = meta
             ctx.ops = ops
             ctx.in_dtypes = [o.dtype for o in operands]
             ctx.root_rescaled = bool(resc[plan.n_steps - 1] > 0) if len(resc) else True
+            if info is not None:
+                info["root_rescaled"] = ctx.root_rescaled
             if plain:
                 return out
             return out, log_scale
@@ -282,17 +312,111 @@ def _function(torch):
         @staticmethod
         @once_differentiable
         def backward(ctx, *grads):
-            plan, dtype, plain, contract_list = ctx.meta
+            plan, dtype, plain, contract_list, ssa, _info = ctx.meta
             shapes = tuple(tuple(o.shape) for o in ctx.ops)
-            sch = backward_schedule(contract_list, shapes, dtype.name, not plain)
+            if ssa is None:
+                sch = backward_schedule(contract_list, shapes, dtype.name, not plain)
+            else:
+                sch = ssa_backward_schedule(ssa, shapes, dtype.name, not plain)
             g_t = grads[0]
             g_c = None if plain else grads[1]
             inputs = _backward(torch, sch, ctx.ops, ctx.in_dtypes, ctx.needs_input_grad[1:], g_t, g_c,
                                ctx.root_rescaled)
             return (None,) + tuple(inputs)
 
-    _FN.append(ContractFunction)
+    class CplxNormalizeFunction(torch.autograd.Function):
+        """``(T_e, c_e) -> (T, c)`` of `cplx_normalize` on the real views of a complex result."""
+
+        @staticmethod
+        def forward(ctx, meta, t_e, c_e):
+            rescaled, dtype = meta
+            t, c, rho = cplx_normalize(torch, t_e, c_e, rescaled, dtype)
+            ctx.set_materialize_grads(False)
+            ctx.meta = meta
+            ctx.rho = rho
+            ctx.save_for_backward(t)
+            return t, c
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g_t, g_c):
+            rescaled, dtype = ctx.meta
+            if not rescaled or (g_t is None and g_c is None):     # the identity (or nothing to pass down)
+                return None, g_t, g_c
+            (t,) = ctx.saved_tensors
+            return None, _cplx_normalize_grad(torch, t, g_t, g_c, ctx.rho, dtype), g_c
+
+    _FN.extend([ContractFunction, CplxNormalizeFunction])
     return ContractFunction
+
+
+def cplx_normalize_with_grad(t_e, c_e, rescaled, dtype):
+    """`cplx_normalize` as a differentiable step: its backward is `ctn_cplx_normalize_grad`."""
+    import torch
+
+    _function(torch)
+    return _FN[1].apply((bool(rescaled), np.dtype(dtype)), t_e, c_e)
+
+
+# ---------------------------------------------------------------------------
+# complex results: the reference's normalisation by the mean modulus (include/ctn_abi.h, ctn_cplx_*)
+# ---------------------------------------------------------------------------
+def cplx_normalize(torch, t_e, c_e, rescaled, dtype, in_place=False):
+    """``(T, c, rho)``: the plan's split result ``(T_e, c_e)`` of a complex network - ``T_e`` the real view ``[..., 2]``,
+    ``c_e`` its 0-d register, both on the device - brought to the reference's normalisation by the mean modulus when
+    the plan rescaled its root (``rescaled``), else left as it is.  ``in_place``: ``T`` is ``T_e``."""
+    dev = t_e.device
+    stream, side = _stream_for(torch, dev)
+    with torch.cuda.stream(side) if side is not None else _NullCtx():
+        if side is not None:
+            t_e.record_stream(side)
+            c_e.record_stream(side)
+        t = t_e if in_place else torch.empty_like(t_e, memory_format=torch.contiguous_format)
+        c = torch.empty((), dtype=c_e.dtype, device=dev)
+        rho = torch.empty(1, dtype=torch.float64, device=dev)
+        scratch = torch.empty(engine.CPLX_SCRATCH, dtype=torch.float64, device=dev) if rescaled else None
+        with einsum._locked_executor(einsum._service_plan(), 1, device=dev.index or 0, stream=stream) as ex:
+            ex.cplx_normalize(dtype, t_e.data_ptr(), c_e.data_ptr(), rescaled, t_e.numel() // 2, t.data_ptr(),
+                              c.data_ptr(), rho.data_ptr(), scratch.data_ptr() if scratch is not None else 0)
+    _rejoin(torch, dev, side, (t, c, rho))
+    return t, c, rho
+
+
+def _cplx_normalize_grad(torch, t, g_t, g_c, rho, dtype):
+    """Cotangent of ``T_e`` behind a rescaled `cplx_normalize` (``g_t`` / ``g_c`` may be None)."""
+    dev = t.device
+    stream, side = _stream_for(torch, dev)
+    with torch.cuda.stream(side) if side is not None else _NullCtx():
+        if side is not None:
+            for x in (t, g_t, g_c, rho):
+                if x is not None:
+                    x.record_stream(side)
+
+        def dense(x):
+            if x is None:
+                return None
+            x = x.to(device=dev, dtype=t.dtype).contiguous()
+            return x.clone() if x.data_ptr() % 16 else x
+
+        g_t, g_c = dense(g_t), dense(g_c)
+        out = torch.empty(t.shape, dtype=t.dtype, device=dev)
+        scratch = torch.empty(engine.CPLX_SCRATCH, dtype=torch.float64, device=dev)
+        with einsum._locked_executor(einsum._service_plan(), 1, device=dev.index or 0, stream=stream) as ex:
+            ex.cplx_normalize_grad(dtype, t.data_ptr(), g_t.data_ptr() if g_t is not None else 0,
+                                   g_c.data_ptr() if g_c is not None else 0, rho.data_ptr(), t.numel() // 2,
+                                   out.data_ptr(), scratch.data_ptr())
+    _rejoin(torch, dev, side, (out,))
+    return out
+
+
+def _rejoin(torch, dev, side, results):
+    """After work on a side stream (`_stream_for`): order torch's current stream after it, hand it the results."""
+    if side is None:
+        return
+    cur = torch.cuda.current_stream(dev)
+    cur.wait_stream(side)
+    for t in results:
+        t.record_stream(cur)
 
 
 def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_rescaled):

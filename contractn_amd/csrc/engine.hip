@@ -39,6 +39,7 @@
 #include "kernels_mfma_lat.h"
 #include "kernels_stream.h"
 #include "kernels_grad.h"
+#include "kernels_cplx.h"
 
 namespace ctn {
 
@@ -2415,6 +2416,62 @@ int ctn_grad_leaf(ctn_exec* exec, int src_dtype, const void* src, const double* 
     hipLaunchKernelGGL((k_grad_leaf<double, float>), grid, dim3(256), 0, E->stream, a, (const double*)src, g, (float*)dst);
   else
     hipLaunchKernelGGL((k_grad_leaf<double, double>), grid, dim3(256), 0, E->stream, a, (const double*)src, g, (double*)dst);
+  HIPCHECK(hipGetLastError());
+  return CTN_OK;
+}
+
+static_assert(kCplxBlocks <= CTN_CPLX_SCRATCH, "one scratch double per workgroup of the complex reductions");
+static bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
+
+int ctn_cplx_normalize(ctn_exec* exec, int dtype, const void* t_e, const void* c_e, int rescaled, int64_t numel,
+                       void* t, void* c, double* rho_out, double* scratch) {
+  if (!exec || !t_e || !c_e || !t || !c || !rho_out || (rescaled && !scratch) || numel < 1) {
+    g_err = "invalid argument to ctn_cplx_normalize";
+    return CTN_INVALID_ARG;
+  }
+  if (dtype != CTN_F32 && dtype != CTN_F64) { g_err = "ctn_cplx_normalize: dtype must be f32 or f64"; return CTN_UNSUPPORTED; }
+  Exec* E = &exec->e;
+  DeviceGuard dg(E->device);
+  HIPCHECK(dg.err);
+  const int vec = aligned16(t_e) && aligned16(t) ? 1 : 0;
+  const int64_t items = vec ? (2 * numel * (dtype == CTN_F32 ? 4 : 8) + 15) / 16 : numel;
+  const int nb = (int)std::min<int64_t>((items + 255) / 256, kCplxBlocks);
+  const int parts = rescaled ? nb : 0;
+  const dim3 ga((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 4096)));
+  if (dtype == CTN_F32) {
+    if (rescaled) hipLaunchKernelGGL(k_cplx_abs_sum<float>, dim3(nb), dim3(256), 0, E->stream, (const float*)t_e, numel, vec, scratch);
+    hipLaunchKernelGGL(k_cplx_normalize<float>, ga, dim3(256), 0, E->stream, (const float*)t_e, (float*)t, numel, vec,
+                       (const double*)scratch, parts, rescaled ? 1 : 0, (const float*)c_e, (float*)c, rho_out);
+  } else {
+    if (rescaled) hipLaunchKernelGGL(k_cplx_abs_sum<double>, dim3(nb), dim3(256), 0, E->stream, (const double*)t_e, numel, vec, scratch);
+    hipLaunchKernelGGL(k_cplx_normalize<double>, ga, dim3(256), 0, E->stream, (const double*)t_e, (double*)t, numel, vec,
+                       (const double*)scratch, parts, rescaled ? 1 : 0, (const double*)c_e, (double*)c, rho_out);
+  }
+  HIPCHECK(hipGetLastError());
+  return CTN_OK;
+}
+
+int ctn_cplx_normalize_grad(ctn_exec* exec, int dtype, const void* t, const void* g_t, const void* g_c,
+                            const double* rho, int64_t numel, void* g_te, double* scratch) {
+  if (!exec || !t || !rho || !g_te || !scratch || numel < 1) { g_err = "invalid argument to ctn_cplx_normalize_grad"; return CTN_INVALID_ARG; }
+  if (dtype != CTN_F32 && dtype != CTN_F64) { g_err = "ctn_cplx_normalize_grad: dtype must be f32 or f64"; return CTN_UNSUPPORTED; }
+  Exec* E = &exec->e;
+  DeviceGuard dg(E->device);
+  HIPCHECK(dg.err);
+  const int vec = aligned16(t) && aligned16(g_t) && aligned16(g_te) ? 1 : 0;
+  const int64_t items = vec ? (2 * numel * (dtype == CTN_F32 ? 4 : 8) + 15) / 16 : numel;
+  const int nb = (int)std::min<int64_t>((items + 255) / 256, kCplxBlocks);
+  const int parts = g_t ? nb : 0;
+  const dim3 ga((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 4096)));
+  if (dtype == CTN_F32) {
+    if (g_t) hipLaunchKernelGGL(k_cplx_grad_dot<float>, dim3(nb), dim3(256), 0, E->stream, (const float*)g_t, (const float*)t, numel, vec, scratch);
+    hipLaunchKernelGGL(k_cplx_grad_apply<float>, ga, dim3(256), 0, E->stream, (const float*)g_t, (const float*)t, numel, vec,
+                       (const double*)scratch, parts, (const float*)g_c, rho, (float*)g_te);
+  } else {
+    if (g_t) hipLaunchKernelGGL(k_cplx_grad_dot<double>, dim3(nb), dim3(256), 0, E->stream, (const double*)g_t, (const double*)t, numel, vec, scratch);
+    hipLaunchKernelGGL(k_cplx_grad_apply<double>, ga, dim3(256), 0, E->stream, (const double*)g_t, (const double*)t, numel, vec,
+                       (const double*)scratch, parts, (const double*)g_c, rho, (double*)g_te);
+  }
   HIPCHECK(hipGetLastError());
   return CTN_OK;
 }

@@ -360,7 +360,7 @@ def _core_contract(operands, contract_list, backend="numpy", _plain=False, **ein
     dtype = _common_dtype(operands, backend, einsum_kwargs.get("dtype"))
     shapes = tuple(tuple(int(d) for d in op.shape) for op in operands)
     if _is_complex(operands, backend):
-        return _core_contract_complex(operands, contract_list, shapes, dtype, backend)
+        return _core_contract_complex(operands, contract_list, shapes, dtype, backend, plain=_plain)
     plan = _native_plan(contract_list, shapes, dtype.name)
     if backend == "torch":
         return _run_torch(plan, operands, dtype, plain=_plain, contract_list=contract_list)
@@ -394,7 +394,8 @@ def _complex_plan_cached(contract_list, shapes, is_cplx, dtype_name):
     of every element), then ONE real GEMM with the pair leg as one more contracted label does the step.  A real operand
     meeting a complex one needs nothing (the pair leg rides along as a free label).  The reference reaches complex
     arithmetic through NumPy (einsum.py:371-384; SURVEY.md App. A row complex128); here it is four real multiply-adds per
-    complex one on the same kernels.  Returns ``(plan, S inputs appended, result is complex)``."""
+    complex one on the same kernels.  Returns ``(plan, S inputs appended, result is complex, (in_labels, steps))`` - the
+    last the plan's SSA form, from which the backward schedule is built (`autograd.BackwardSchedule.from_ssa`)."""
     n = len(shapes)
     in_labels, steps = lower_contraction_list(n, contract_list, shapes)
     sizes = {}
@@ -466,13 +467,15 @@ def _complex_plan_cached(contract_list, shapes, is_cplx, dtype_name):
         labels_of[n + k] = out + ((cplx[n + k],) if n + k in cplx else ())
         remap[n + k] = n_in + len(new_steps) - 1
     plan = engine.Plan(dtype_name, new_in_labels, new_shapes, new_steps, stabilize=True, min_norm=MIN_NORM)
-    return plan, n_s, (n + len(steps) - 1) in cplx
+    ssa = (tuple(tuple(lab) for lab in new_in_labels), tuple((a, b, tuple(o)) for a, b, o in new_steps))
+    return plan, n_s, (n + len(steps) - 1) in cplx, ssa
 
 
-def _core_contract_complex(operands, contract_list, shapes, dtype, backend):
+def _core_contract_complex(operands, contract_list, shapes, dtype, backend, plain=False):
     """`_core_contract` for networks with complex operands (see `_complex_plan_cached`).  The engine normalises by the
     mean of |re| + |im|; the reference by the mean modulus (einsum.py:97 ``abs``): the final tensor is brought to the
-    reference's normalisation here - one pass over the result - and the register moves by the log of the ratio."""
+    reference's normalisation - one pass over the result - and the register moves by the log of the ratio.  Torch
+    operands that are all on the device stay there (`_complex_torch_device`); everything else runs through the host."""
     if backend == "torch":
         import torch
 
@@ -481,7 +484,9 @@ def _core_contract_complex(operands, contract_list, shapes, dtype, backend):
         operands = [np.asarray(o) for o in operands]
         is_c = tuple(o.dtype.kind == "c" for o in operands)
     with _PLAN_LOCK:
-        plan, n_s, out_complex = _complex_plan_cached(contract_list, shapes, is_c, dtype.name)
+        plan, n_s, out_complex, ssa = _complex_plan_cached(contract_list, shapes, is_c, dtype.name)
+    if backend == "torch" and all(o.is_cuda for o in operands):
+        return _complex_torch_device(plan, n_s, out_complex, ssa, operands, is_c, dtype, plain, contract_list)
     cdt = np.dtype(np.complex64 if dtype == np.float32 else np.complex128)
     if backend == "torch":
         tdt = torch.float32 if dtype == np.float32 else torch.float64
@@ -515,6 +520,53 @@ def _core_contract_complex(operands, contract_list, shapes, dtype, backend):
     if backend == "torch":
         return torch.from_numpy(np.array(res)).to(dev), torch.tensor(float(log_scale), dtype=tdt, device=dev)
     return res, log_scale
+
+
+_CSTRUCT_DEV = {}
+
+
+def _cstruct_on(torch, dev, tdt):
+    """The structure tensor S on ``dev`` in ``tdt`` (cached per device and dtype; it never needs a gradient)."""
+    key = (str(dev), tdt)
+    s = _CSTRUCT_DEV.get(key)
+    if s is None:
+        s = _CSTRUCT_DEV.setdefault(key, torch.tensor(_CSTRUCT, dtype=tdt, device=dev))
+    return s
+
+
+@lru_cache(maxsize=None)
+def _service_plan():
+    """A one-element plan: its executors only carry launches of free-standing kernels (`ctn_cplx_*`) on a stream."""
+    return engine.Plan(np.float32, [(0,)], [(1,)], [(0, -1, (0,))], stabilize=True, min_norm=MIN_NORM)
+
+
+def _complex_torch_device(plan, n_s, out_complex, ssa, operands, is_c, dtype, plain, contract_list):
+    """A complex network of device tensors, on the device: the real plan on zero-copy ``view_as_real`` views of the
+    complex operands (real operands as they are), then - split format - `autograd.cplx_normalize` to the reference's
+    normalisation, or - plain - the de-stabilised value of the finish pass (it does not depend on the normalisation).
+    With operands that require grad the same pieces run as autograd Functions (`autograd.contract_with_grad` over the
+    lowered plan, `autograd.cplx_normalize_with_grad`); gradients reach complex operands through ``view_as_real``."""
+    import torch
+
+    from . import autograd
+
+    tdt = torch.float32 if dtype == np.float32 else torch.float64
+    dev = operands[0].device
+    ops = [torch.view_as_real(o.resolve_conj().contiguous()) if c else o for o, c in zip(operands, is_c)]
+    ops += [_cstruct_on(torch, dev, tdt)] * n_s
+    if torch.is_grad_enabled() and any(o.requires_grad for o in operands):
+        info = {}
+        out, log_scale = autograd.contract_with_grad(plan, ops, dtype, plain, contract_list, ssa=ssa, info=info)
+        if not plain and out_complex:
+            out, log_scale = autograd.cplx_normalize_with_grad(out, log_scale, info["root_rescaled"], dtype)
+    else:
+        out, log_scale, resc, _ops = _run_torch_device(plan, ops, dtype, plain)
+        if not plain and out_complex:
+            rescaled = bool(resc[plan.n_steps - 1] > 0)
+            out, log_scale, _rho = autograd.cplx_normalize(torch, out, log_scale, rescaled, dtype, in_place=True)
+    if out_complex:
+        out = torch.view_as_complex(out)
+    return out, log_scale
 
 
 def _run_torch(plan, operands, dtype, plain=False, contract_list=None):

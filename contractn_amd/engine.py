@@ -42,9 +42,11 @@ ABI_SYMBOLS = (
     "ctn_exec_add_scales", "ctn_exec_merge_scales", "ctn_exec_report_suspect",
     "ctn_exec_set_finish_mode", "ctn_exec_finish",
     "ctn_grad_seed", "ctn_grad_leaf",
+    "ctn_cplx_normalize", "ctn_cplx_normalize_grad",
 )
 GRAD_SCRATCH = 512          # doubles of scratch ctn_grad_seed needs (CTN_GRAD_SCRATCH)
 GRAD_MAX_DIMS = 64          # axes of an operand ctn_grad_leaf writes (CTN_GRAD_MAX_DIMS)
+CPLX_SCRATCH = 1024         # doubles of scratch ctn_cplx_normalize(_grad) needs (CTN_CPLX_SCRATCH)
 
 
 class PlanDesc(C.Structure):
@@ -171,6 +173,8 @@ def load_library():
         "ctn_grad_seed": (i32, [vp, i32, vp, vp, vp, vp, vp, i64, f64, vp, vp, vp]),
         "ctn_grad_leaf": (i32, [vp, i32, vp, vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                 C.POINTER(C.c_int32), i32, vp]),
+        "ctn_cplx_normalize": (i32, [vp, i32, vp, vp, i32, i64, vp, vp, vp, vp]),
+        "ctn_cplx_normalize_grad": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -520,6 +524,22 @@ class Executor:
                                        C.c_void_p(src_ptr), C.c_void_p(g_ptr or None), len(d), _ptr(d, C.c_int64),
                                        _ptr(st, C.c_int64), _ptr(fi, C.c_int32),
                                        CTN_F32 if np.dtype(dst_dtype) == np.float32 else CTN_F64, C.c_void_p(dst_ptr)))
+
+    # -- complex results (include/ctn_abi.h, ctn_cplx_*): kernels on this executor's stream ----------------------
+    def cplx_normalize(self, dtype, t_e_ptr, c_e_ptr, rescaled, numel, t_ptr, c_ptr, rho_ptr, scratch_ptr):
+        """Enqueue ``(t, c) = (t_e / rho, c_e + log rho)`` with ``rho`` the mean modulus of the ``numel`` complex elements
+        of ``t_e`` (components of ``dtype``), or ``(t_e, c_e)`` when ``rescaled`` is false; ``rho`` goes to ``rho_ptr``."""
+        code = CTN_F32 if np.dtype(dtype) == np.float32 else CTN_F64
+        _check(self._lib.ctn_cplx_normalize(self._h, code, C.c_void_p(t_e_ptr), C.c_void_p(c_e_ptr), 1 if rescaled else 0,
+                                            int(numel), C.c_void_p(t_ptr), C.c_void_p(c_ptr), C.c_void_p(rho_ptr),
+                                            C.c_void_p(scratch_ptr or None)))
+
+    def cplx_normalize_grad(self, dtype, t_ptr, g_t_ptr, g_c_ptr, rho_ptr, numel, g_te_ptr, scratch_ptr):
+        """Enqueue the cotangent of ``t_e`` behind a rescaled `cplx_normalize` (``g_t_ptr`` / ``g_c_ptr`` may be 0)."""
+        code = CTN_F32 if np.dtype(dtype) == np.float32 else CTN_F64
+        _check(self._lib.ctn_cplx_normalize_grad(self._h, code, C.c_void_p(t_ptr), C.c_void_p(g_t_ptr or None),
+                                                 C.c_void_p(g_c_ptr or None), C.c_void_p(rho_ptr), int(numel),
+                                                 C.c_void_p(g_te_ptr), C.c_void_p(scratch_ptr)))
 
     def set_timing(self, slots):
         """Bracket every step of the next ``slots`` enqueues with HIP events (0 = off)."""

@@ -303,6 +303,29 @@ int ctn_grad_seed(ctn_exec* exec, int dtype, const void* t_hat, const void* g_ha
 int ctn_grad_leaf(ctn_exec* exec, int src_dtype, const void* src, const double* g, int ndim, const int64_t* dims,
                   const int64_t* src_strides, const int32_t* first, int dst_dtype, void* dst);
 
+/*
+ * Complex results.  A complex network runs as a real plan on (re, im) components, whose stabilisation
+ * normalises by the mean of |re| + |im|; the reference normalises by the mean modulus.  These bring the plan's finished
+ * split result (t_e, c_e) to the reference's (t, c) and back-propagate through that map.  Tensors are numel complex
+ * elements stored as interleaved (re, im) pairs with components of `dtype` (CTN_F32: complex64, CTN_F64: complex128);
+ * registers are one element of `dtype`.  Both run on the stream of `exec` (any executor of the caller's device and
+ * stream); all pointers are device pointers.  Every sum runs in a fixed order (bit-reproducible).
+ *
+ * ctn_cplx_normalize: rescaled != 0 (the plan rescaled its root): rho = sum|t_e| / numel (moduli summed in double, the
+ *   quotient rounded to dtype), t = t_e / rho, c = c_e + log(rho) in dtype, *rho_out = rho.  rescaled == 0: t = t_e,
+ *   c = c_e, *rho_out = 1.  t may be t_e (in place).  scratch: CTN_CPLX_SCRATCH doubles (may be NULL when rescaled == 0).
+ * ctn_cplx_normalize_grad: the cotangent g_te of t_e from the cotangents g_t of t and g_c of c after a rescaled
+ *   ctn_cplx_normalize with result t and factor *rho:
+ *     g_te = [g_t - (<g_t, t> - g_c) u / numel] / rho,   u = t / |t| (0 where t = 0),
+ *   <,> the real dot product of the pairs; the cotangent of c_e is g_c itself.  g_t, g_c may be NULL (= 0).
+ *   scratch: CTN_CPLX_SCRATCH doubles.
+ */
+#define CTN_CPLX_SCRATCH 1024
+int ctn_cplx_normalize(ctn_exec* exec, int dtype, const void* t_e, const void* c_e, int rescaled, int64_t numel,
+                       void* t, void* c, double* rho_out, double* scratch);
+int ctn_cplx_normalize_grad(ctn_exec* exec, int dtype, const void* t, const void* g_t, const void* g_c,
+                            const double* rho, int64_t numel, void* g_te, double* scratch);
+
 #ifdef __cplusplus
 }
 #endif
