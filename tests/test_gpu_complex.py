@@ -20,11 +20,12 @@ GOLDEN_COMPLEX = ["mps_overlap_5x12x3_c128", "mps_overlap_4x40x4_c64", "mps_over
                   "mps_open_random_c128", "cp_r5_c128"]
 
 
-def ref_contract(einstr, ops, path, split_format, decide="modulus"):
+def ref_contract(einstr, ops, path, split_format, decide="modulus", on_step=None):
     """reference einsum.py:326-393 + 89-114 on CPU torch tensors with complex operands: the register is real (the
     reference's torch backend: float32 for complex64, float64 for complex128), the norm the sum of moduli.  Real operands
     are promoted to the network's complex dtype (the result of torch.einsum on mixed operands).  ``decide="l1"``: the
-    rescale decisions on the sum of |re| + |im| instead (the engine's), the normalisation unchanged."""
+    rescale decisions on the sum of |re| + |im| instead (the engine's), the normalisation unchanged.
+    ``on_step(sum of moduli, rescaled)`` is called after every step (guards on the inputs of a test)."""
     wide = any(o.dtype in (torch.float64, torch.complex128) for o in ops)
     cdt = torch.complex128 if wide else torch.complex64
     rdt = torch.float64 if wide else torch.float32
@@ -41,6 +42,8 @@ def ref_contract(einstr, ops, path, split_format, decide="modulus"):
         cond = (norm if decide == "modulus" else (new.real.abs() + new.imag.abs()).sum()) > 1e-7
         new = torch.where(cond, new / rescale, new)
         log_scale = torch.where(cond, log_scale + torch.log(rescale), log_scale)
+        if on_step is not None:
+            on_step(float(norm.detach()), bool(cond.detach()))
         operands.append(new)
     if split_format:
         return operands[0], log_scale

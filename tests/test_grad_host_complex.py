@@ -115,3 +115,56 @@ def test_complex_fixtures_load_with_complex_dtypes_and_the_recorded_shapes(name)
         assert [g.shape for g in fx["gps"]] == [op.shape for op in fx["operands"]]
     else:
         assert name == "chain200"              # its plain value overflows: split format only
+
+
+# ---- the networks of tests/test_gpu_complex_kernels.py reach the kernel forms they are about ------------------------
+from tests import grad_cases as GC                                               # noqa: E402
+from tests import grad_cases_complex as GCC                                      # noqa: E402
+
+KERNEL_DTYPES = ["float32", "float64"]
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("dtype", KERNEL_DTYPES)
+@pytest.mark.parametrize("name", sorted(GCC.COMPLEX_KERNEL_NETWORKS))
+def test_complex_kernel_networks_reach_their_forms(name, dtype, split):
+    assert set(GCC.FORMS) == set(GCC.COMPLEX_KERNEL_NETWORKS)
+    assert any(dt == dtype for _w, _s, _p, dt in GCC.FORMS[name]), (name, dtype)
+    assert GCC.missing_forms(name, dtype, split) == []
+
+
+@pytest.mark.parametrize("split", [True, False])
+def test_complex_kernel_networks_cover_the_kernels_between_them(split):
+    fwd, bwd = {"float32": [], "float64": []}, {"float32": [], "float64": []}
+    for name in GCC.COMPLEX_KERNEL_NETWORKS:
+        for dt in KERNEL_DTYPES:
+            f, rec, cot = GCC.network_forms(name, dt, split)
+            fwd[dt] += [dict(i, case=name) for i in f]
+            bwd[dt] += [dict(i, case=name) for i in rec + cot]
+    f32, f64 = fwd["float32"] + bwd["float32"], fwd["float64"] + bwd["float64"]
+    assert any(i["kernel"] == 2 and GCC.modes(i, 0, 0) and GCC.tile128(i) and i["k"] >= 1024 for i in f32)
+    assert any(GC.large(i, 1, 1) and i["case"] == "cmps6_mixed" for i in f32)
+    assert any(i["kernel"] == 3 and GCC.tile128(i) and i["k"] == 2048 for i in f64)
+    assert any(GC.ragged(i) for i in f32) and any(GC.ragged(i) for i in f64)
+    assert any(i["kernel"] == 4 for i in f32) and any(i["kernel"] == 4 for i in f64)
+    assert any(i["kernel"] == 5 for i in f32)
+    for dt in KERNEL_DTYPES:                      # the streaming S step, at least 2^18 rows, in each direction
+        assert any(i["kernel"] == 0 and i["m"] >= 262144 and (i["n"], i["k"]) == (4, 2) for i in fwd[dt])
+        assert any(i["kernel"] == 0 and i["m"] >= 262144 and (i["n"], i["k"]) == (2, 4) for i in bwd[dt])
+
+
+def test_complex_kernel_walk_skips_the_s_inputs():
+    """No cotangent step of any case ends in an S input (`complex_step_infos` asserts it while walking), and the S
+    inputs are there: every complex x complex case has at least one."""
+    for name, make in GCC.COMPLEX_KERNEL_NETWORKS.items():
+        einstr, shapes, path, is_c = make()
+        _plan, n_s, out_c, _ssa = GCC.lowered(einstr, shapes, path, is_c, "float32")
+        assert out_c, name
+        both = sum(is_c) >= 2
+        assert (n_s > 0) == both, (name, n_s)
+
+
+def test_complex_forms_notice_a_shrunk_network(monkeypatch):
+    monkeypatch.setitem(GCC.COMPLEX_KERNEL_NETWORKS, "cmps6_D256", lambda: GCC._mps([32] * 5, 4))
+    for dt in KERNEL_DTYPES:
+        assert GCC.missing_forms("cmps6_D256", dt, True), dt

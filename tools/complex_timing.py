@@ -6,7 +6,10 @@
 * ``normalize``: device-event time and achieved TB/s of ``ctn_cplx_normalize`` (rescaled, out of place) and
   ``ctn_cplx_normalize_grad`` on a 2^27-element complex64 result, against the 8.0 TB/s HBM3E peak of the MI355X.
 
-Every figure: warm-up calls first, then ``--reps`` timed calls; median, min and max reported.
+Every figure: warm-up calls first, then ``--reps`` timed calls; median, min and max reported.  This tool times:
+``device_vs_host_abs_diff`` compares two runs of the same engine and is no correctness check - that is
+tests/test_gpu_complex_kernels.py (complex networks at kernel-scale shapes and these two kernels against CPU
+references).
 
     python tools/complex_timing.py [--sites 100] [--bond 128] [--reps 20] [--warmup 3] [--log2-numel 27]
 """
