@@ -34,6 +34,7 @@
 #include "kernels_mfma_ares.h"
 #include "kernels_zip.h"
 #include "kernels_zip64.h"
+#include "kernels_zip_f64.h"
 #include "kernels_zipl.h"
 #include "kernels_sweep.h"
 #include "kernels_mfma_lat.h"
@@ -67,7 +68,8 @@ struct DevSwitches {
   int sweep = -1;        // CTN_SWEEP: 0 never walk a chain of epilogue-summed steps in one launch (k_sweep_f32), 1 whenever one matches (tests)
   int dot_tr = 1;        // CTN_DOT_TR=0: full dots against a transposed tensor stay on k_dot_split's 4-byte gathers
   int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches
-                         // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32)
+                         // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
+                         // (k_zip_f64) whenever the pair matches; 2 has no fp64 meaning and keeps the two-launch path
   int zipl = -1;         // CTN_ZIPL: 0 never run a zipper pair as one latency-form launch (k_zip_lat), 1 whenever the pair matches (tests)
   int zipl_max_r = 8;    // CTN_ZIPL_MAX_R: most networks in flight for which k_zip_lat is taken by default (100-site D = 256
                          // network, ms per pass, k_zip_lat / per-step launches: R = 1 1.40 / 2.05, 2: 1.58 / 3.3, 4: 2.1 / 3.5,
@@ -158,7 +160,7 @@ struct Exec {
   // zipper pairs (kernels_zip.h): zip[s2] describes the fused launch of steps (s2 - 1, s2); zip_skip[s1] = the first
   // step of such a pair is never launched (its result only exists in the fused kernel's registers)
   struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
-                   int zu = 128; };      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32)
+                   int zu = 128; bool f64 = false; };   // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
   std::vector<ZipDesc> zip;
   std::vector<char> zip_skip;
   // the same pairs in their latency form (kernels_zipl.h): zl[s2] = the fused launch of steps (s2 - 1, s2), whose result
@@ -580,20 +582,27 @@ static void launch_splitk_reduce(Exec* E, int partials, int R, const StepArgs& a
   hipLaunchKernelGGL(k_splitk_reduce<T>, dim3(partials, R), dim3(256), 0, E->stream, a, sk);
 }
 
-// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 can run as one launch?  Checked on the plan's own offset
-// tables (every operand dense along its innermost index with uniform strides), so nothing about the network's labels
-// is assumed: T = E . X with |m1| = 256 rows from E, columns (q, u) from X; E' = T . Y contracting (m1, q), |n2| = 256.
-static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int u_mult = ZU) {
-  if (s2 < 1 || s2 + 1 >= P.n_steps || P.dtype != CTN_F32) return false;
+// Is k_zip_f64 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
+static constexpr bool kZipF64Default = false;
+
+// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32) or k_zip_f64 (CTN_F64) can run as one launch?
+// Checked on the plan's own offset tables (every operand dense along its innermost index with uniform strides), so
+// nothing about the network's labels is assumed: T = E . X with |m1| = 256 rows from E, columns (q, u) from X;
+// E' = T . Y contracting (m1, q), |n2| = 256.  The element type decides the kernel kind of the two steps, the depth of a
+// phase-1 tile and - fp64: 16-byte requests and stores of pairs of doubles - that every leading dimension is even.
+static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_mult = ZU) {
+  if (s2 < 1 || s2 + 1 >= P.n_steps || P.dtype != dtype || (dtype != CTN_F32 && dtype != CTN_F64)) return false;
+  const bool f64 = dtype == CTN_F64;
+  const int kt = f64 ? ZDK : ZK;
   const Step& a = P.steps[s2 - 1];
   const Step& b = P.steps[s2];
   auto plain = [&](const Step& st) {
-    return st.kernel == CTN_KERNEL_MFMA_F32 && st.Bt == 1 && st.rhs >= 0 && st.lhs2 < 0 && !st.epw && st.modeA == 1 &&
+    return st.kernel == (f64 ? CTN_KERNEL_MFMA_F64 : CTN_KERNEL_MFMA_F32) && st.Bt == 1 && st.rhs >= 0 && st.lhs2 < 0 && !st.epw && st.modeA == 1 &&
            st.modeB == 1 && !st.collapse;
   };
   if (!plain(a) || !plain(b) || b.lhs != a.out || !b.cvec) return false;
   if (a.rhs >= P.n_inputs || b.rhs >= P.n_inputs) return false;            // X and Y: network inputs (scale 1)
-  if (a.M != ZM || b.N != ZM || a.K % ZK != 0 || a.K < 2 * ZK || a.N % u_mult != 0) return false;
+  if (a.M != ZM || b.N != ZM || a.K % kt != 0 || a.K < 2 * kt || a.N % u_mult != 0) return false;
   const int32_t* T = P.tables.data();
   const int32_t *omA = T + a.t.omA, *okA = T + a.t.okA, *onB = T + a.t.onB, *okB = T + a.t.okB, *omC = T + a.t.omC, *onC = T + a.t.onC;
   const int64_t N1 = a.N;
@@ -628,7 +637,8 @@ static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int u_mult = ZU) 
     if (okB2[k] != q * ldYq + m1 * ldYm || seen[(size_t)(m1 * Q + q)]) return false;
     seen[(size_t)(m1 * Q + q)] = 1;
   }
-  z->on = true; z->ldE = ldE; z->ldXq = ldXq; z->ldXk = ldXk; z->ldYq = ldYq; z->ldYm = ldYm; z->ldC = ldC;
+  if (f64 && ((ldE | ldXq | ldXk | ldYq | ldYm | ldC) & 1)) return false;
+  z->on = true; z->f64 = f64; z->ldE = ldE; z->ldXq = ldXq; z->ldXk = ldXk; z->ldYq = ldYq; z->ldYm = ldYm; z->ldC = ldC;
   z->Q = (int)Q; z->U = (int)U; z->K1 = (int)a.K;
   return true;
 }
@@ -993,7 +1003,9 @@ static int exec_launch_steps(Exec* E) {
       const size_t ez = timed_z ? ((size_t)E->timing_runs * P.n_steps + s) * 2 : 0;
       if (timed_z) HIPCHECK(hipEventRecord(E->events[ez], E->stream));
       if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-      E->launched_tile[s] = (512 << 16) | (zd.zu == 64 ? 128 : 256);   // the fused pair: 128 (or 64) values of u x all 256 n2 per workgroup
+      // the fused pair: 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256):
+      // an fp64 step with 128 tile columns reads as k_mfma_f64_g
+      E->launched_tile[s] = (512 << 16) | ((zd.zu == 64 && !zd.f64) ? 128 : 256);
       const int per = zd.U / zd.zu;
       if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
         const size_t need = (size_t)per * R;
@@ -1005,13 +1017,18 @@ static int exec_launch_steps(Exec* E) {
         z.dbg = E->d_dbg;
         HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
       }
-      if (zd.zu == 64) hipLaunchKernelGGL(k_zip64_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
+      if (zd.f64) hipLaunchKernelGGL(k_zip_f64, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
+      else if (zd.zu == 64) hipLaunchKernelGGL(k_zip64_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       else hipLaunchKernelGGL(k_zip_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       if (E->eager_rescale && P.stabilize && s + 1 < P.n_steps) {
         const int64_t numel = P.tensors[st.out].numel;
-        const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / 4 + 255) / 256, 2048)), R);
-        hipLaunchKernelGGL(k_renorm<float>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
-                           (const double*)z.partC, E->step_partials[s], E->step_partials[s], P.min_norm);
+        const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / (zd.f64 ? 2 : 4) + 255) / 256, 2048)), R);
+        if (zd.f64)
+          hipLaunchKernelGGL(k_renorm<double>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
+                             (const double*)z.partC, E->step_partials[s], E->step_partials[s], P.min_norm);
+        else
+          hipLaunchKernelGGL(k_renorm<float>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
+                             (const double*)z.partC, E->step_partials[s], E->step_partials[s], P.min_norm);
       }
       if (timed_z) HIPCHECK(hipEventRecord(E->events[ez + 1], E->stream));
       continue;
@@ -1757,8 +1774,25 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       // forms - while 64 networks are exactly one round of 64: 13.5 ms against 15.9)
       auto fill = [&](int64_t wgs) { return (double)wgs / (double)(((wgs + E.n_cu - 1) / E.n_cu) * E.n_cu); };
       Exec::ZipDesc z128, z64;
-      const bool m128 = E.sw.zip != 2 && zip_match(P, s, &z128) && (E.sw.zip == 1 || (int64_t)(z128.U / ZU) * replicas >= E.n_cu);
-      const bool m64 = E.sw.zip != 1 && zip_match(P, s, &z64, Z6U) && z64.K1 % Z6K == 0 &&
+      if (P.dtype == CTN_F64) {
+        // fp64: one form, 64 values of u per workgroup (k_zip_f64), and only on request (CTN_ZIP=1).  kZipF64Default is
+        // where the rule of the fp32 forms - at least one round of workgroups, rounds filled to 0.9 - would switch it on
+        // unasked; the measurement that has to decide that is in DESIGN section 10.
+        if (E.sw.zip == 2 || !zip_match(P, s, &z, CTN_F64, ZDU)) continue;
+        const int64_t wgs = (int64_t)(z.U / ZDU) * replicas;
+        if (E.sw.zip != 1 && !(kZipF64Default && wgs >= E.n_cu && fill(wgs) >= 0.9)) continue;
+        if (z.U / ZDU > kMaxPartials) continue;
+        z.zu = ZDU;
+        E.zip[s] = z;
+        E.zip_skip[s - 1] = 1;
+        any = true;
+        E.part_slots -= E.step_partials[s];
+        E.step_partials[s] = z.U / z.zu;
+        E.part_slots += E.step_partials[s];
+        continue;
+      }
+      const bool m128 = E.sw.zip != 2 && zip_match(P, s, &z128, CTN_F32) && (E.sw.zip == 1 || (int64_t)(z128.U / ZU) * replicas >= E.n_cu);
+      const bool m64 = E.sw.zip != 1 && zip_match(P, s, &z64, CTN_F32, Z6U) && z64.K1 % Z6K == 0 &&
                        (E.sw.zip == 2 || (int64_t)(z64.U / Z6U) * replicas >= E.n_cu);
       const double f128 = m128 ? fill((int64_t)(z128.U / ZU) * replicas) : 0.0, f64 = m64 ? fill((int64_t)(z64.U / Z6U) * replicas) : 0.0;
       bool ok = false;
@@ -1789,7 +1823,7 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
     int64_t slab_elems = 0;
     for (int s = 1; s + 1 < P.n_steps; ++s) {
       Exec::ZipDesc z;
-      if (E.zl_skip[s - 1] || (s >= 2 && E.zl[s - 1].on) || !zip_match(P, s, &z, 16)) continue;
+      if (E.zl_skip[s - 1] || (s >= 2 && E.zl[s - 1].on) || !zip_match(P, s, &z, CTN_F32, 16)) continue;
       if (z.K1 != ZM || (z.Q != 4 && z.Q != 2) || z.ldC % 4 || z.ldE % 4 || z.ldXk % 4 || z.ldXq % 4 || z.ldYm % 4 || z.ldYq % 4) continue;
       // the part of m1 a workgroup owns: 32 (8 slabs, 128 workgroups per network at |u| = 256) while that still fits ONE
       // round of workgroups, else 64 (4 slabs, half the workgroups, each with twice the work per byte it loads)

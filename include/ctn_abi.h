@@ -169,7 +169,8 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                  lists, einsum.py:97-106) only where the step ran as a launch of its own.  A step whose result
  *                  never exists in memory reports 0.0 and the NEXT launched step carries the product of both:
  *                    - ctn_step_info.kernel == CTN_KERNEL_FUSED (formed inside its consumer);
- *                    - the first step of a zipper pair run by k_zip_f32 (ctn_exec_step_tile reports (1, 1) for
+ *                    - the first step of a zipper pair run as one launch, in every form of it - k_zip_f32,
+ *                      k_zip64_f32, k_zip_lat (fp32) and k_zip_f64 (fp64) - (ctn_exec_step_tile reports (1, 1) for
  *                      it): (T / s) Y = (T Y) / s, the second step's factor is s_T * s_E' of the reference;
  *                  the members of a sweep (k_sweep_f32, tile (1, 1) as well) DO report the reference's per-step
  *                  factors, reconstructed after the launch (within 2e-5 relative, fp32).
