@@ -650,8 +650,10 @@ static bool sweep_step_shape(const Plan& P, int s, SweepShape* sh) {
   const Step& st = P.steps[s];
   const int D = (int)st.K, Pd = st.epw;
   if (P.dtype != CTN_F32 || st.kernel != CTN_KERNEL_MFMA_F32 || (Pd != 2 && Pd != 4) || st.Bt != 1 ||
-      (st.K != 64 && st.K != 128 && st.K != 256 && st.K != 512) || st.N != (int64_t)D * Pd || st.collapse || s + 1 >= P.n_steps)
+      (st.K != 64 && st.K != 128 && st.K != 256 && st.K != 512) || st.N != (int64_t)D * Pd || s + 1 >= P.n_steps)
     return false;
+  // (st.collapse - the step's OWN launch would have more workgroups than partial slots and leave one collapsed slot - is
+  // no obstacle: a member is never launched, and k_sweep_finish fills however many slots the step has, slot 0 first)
   if (st.rhs < 0 || st.rhs >= P.n_inputs || st.lhs2 < 0 || st.lhs2 >= P.n_inputs) return false;   // W, x: network inputs
   const int32_t* T = P.tables.data();
   const int32_t *omA = T + st.t.omA, *okA = T + st.t.okA, *onB = T + st.t.onB, *okB = T + st.t.okB, *omC = T + st.t.omC,

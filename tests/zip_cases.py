@@ -138,13 +138,13 @@ def chain_net(n_sites, phys, psi_bonds=None):
     return Net("chain", ein, shapes, ssa, pairs, "chain%dx%d_" % (n, phys) + "-".join(map(str, psi_bonds)))
 
 
-def signed_permutation(seed):
-    """P[n2, w]: one entry +-1 per row and per column.  Returns (P, perm, sign): (E' P)[:, perm[j]] = sign[j] E'[:, j]."""
+def signed_permutation(seed, n=ZM):
+    """P[n2, w] (n x n): one entry +-1 per row and per column.  Returns (P, perm, sign): (E' P)[:, perm[j]] = sign[j] E'[:, j]."""
     rng = np.random.default_rng(seed)
-    perm = rng.permutation(ZM)
-    sign = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), size=ZM)
-    P = np.zeros((ZM, ZM), dtype=np.float32)
-    P[np.arange(ZM), perm] = sign
+    perm = rng.permutation(n)
+    sign = rng.choice(np.array([-1.0, 1.0], dtype=np.float32), size=n)
+    P = np.zeros((n, n), dtype=np.float32)
+    P[np.arange(n), perm] = sign
     return P, perm, sign
 
 
