@@ -34,6 +34,7 @@
 #include "kernels_mfma_ares.h"
 #include "kernels_zip.h"
 #include "kernels_zip64.h"
+#include "kernels_zip128.h"
 #include "kernels_zip_f64.h"
 #include "kernels_zipl.h"
 #include "kernels_sweep.h"
@@ -70,6 +71,8 @@ struct DevSwitches {
   int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches
                          // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
                          // (k_zip_f64) whenever the pair matches; 2 has no fp64 meaning and keeps the two-launch path
+  int zip128 = 1;        // CTN_ZIP128=0: never the bond-128 pair kernel (k_zip128_f32), which CTN_ZIP=1 takes for fp32 pairs with
+                         // |m1| = |n2| = 128 that no bond-256 form matches
   int zipl = -1;         // CTN_ZIPL: 0 never run a zipper pair as one latency-form launch (k_zip_lat), 1 whenever the pair matches (tests)
   int zipl_max_r = 8;    // CTN_ZIPL_MAX_R: most networks in flight for which k_zip_lat is taken by default (100-site D = 256
                          // network, ms per pass, k_zip_lat / per-step launches: R = 1 1.40 / 2.05, 2: 1.58 / 3.3, 4: 2.1 / 3.5,
@@ -97,6 +100,7 @@ static DevSwitches read_dev_switches() {
   d.lat = num("CTN_LAT", -1);
   d.hform = num("CTN_H", -1);
   d.zip = num("CTN_ZIP", -1);
+  d.zip128 = num("CTN_ZIP128", 1);
   d.zipl = num("CTN_ZIPL", -1);
   d.zipl_max_r = num("CTN_ZIPL_MAX_R", 8);
   d.zipl_mp = num("CTN_ZIPL_MP", 0);
@@ -160,7 +164,8 @@ struct Exec {
   // zipper pairs (kernels_zip.h): zip[s2] describes the fused launch of steps (s2 - 1, s2); zip_skip[s1] = the first
   // step of such a pair is never launched (its result only exists in the fused kernel's registers)
   struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
-                   int zu = 128; bool f64 = false; };   // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
+                   int zu = 128; bool f64 = false;      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
+                   int zm = 256; };                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128)
   std::vector<ZipDesc> zip;
   std::vector<char> zip_skip;
   // the same pairs in their latency form (kernels_zipl.h): zl[s2] = the fused launch of steps (s2 - 1, s2), whose result
@@ -584,13 +589,16 @@ static void launch_splitk_reduce(Exec* E, int partials, int R, const StepArgs& a
 
 // Is k_zip_f64 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
 static constexpr bool kZipF64Default = false;
+// Is k_zip128_f32 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
+static constexpr bool kZip128Default = false;
 
-// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32) or k_zip_f64 (CTN_F64) can run as one launch?
+// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32; `zm` = 128: k_zip128_f32) or k_zip_f64 (CTN_F64)
+// can run as one launch?
 // Checked on the plan's own offset tables (every operand dense along its innermost index with uniform strides), so
-// nothing about the network's labels is assumed: T = E . X with |m1| = 256 rows from E, columns (q, u) from X;
-// E' = T . Y contracting (m1, q), |n2| = 256.  The element type decides the kernel kind of the two steps, the depth of a
+// nothing about the network's labels is assumed: T = E . X with |m1| = zm rows from E, columns (q, u) from X;
+// E' = T . Y contracting (m1, q), |n2| = zm.  The element type decides the kernel kind of the two steps, the depth of a
 // phase-1 tile and - fp64: 16-byte requests and stores of pairs of doubles - that every leading dimension is even.
-static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_mult = ZU) {
+static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_mult = ZU, int zm = ZM) {
   if (s2 < 1 || s2 + 1 >= P.n_steps || P.dtype != dtype || (dtype != CTN_F32 && dtype != CTN_F64)) return false;
   const bool f64 = dtype == CTN_F64;
   const int kt = f64 ? ZDK : ZK;
@@ -602,11 +610,11 @@ static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_
   };
   if (!plain(a) || !plain(b) || b.lhs != a.out || !b.cvec) return false;
   if (a.rhs >= P.n_inputs || b.rhs >= P.n_inputs) return false;            // X and Y: network inputs (scale 1)
-  if (a.M != ZM || b.N != ZM || a.K % kt != 0 || a.K < 2 * kt || a.N % u_mult != 0) return false;
+  if (a.M != zm || b.N != zm || a.K % kt != 0 || a.K < 2 * kt || a.N % u_mult != 0) return false;
   const int32_t* T = P.tables.data();
   const int32_t *omA = T + a.t.omA, *okA = T + a.t.okA, *onB = T + a.t.onB, *okB = T + a.t.okB, *omC = T + a.t.omC, *onC = T + a.t.onC;
   const int64_t N1 = a.N;
-  for (int i = 0; i < ZM; ++i) if (omA[i] != i || omC[i] != (int64_t)i * N1) return false;     // E rows dense, T = [m1][N1]
+  for (int i = 0; i < zm; ++i) if (omA[i] != i || omC[i] != (int64_t)i * N1) return false;     // E rows dense, T = [m1][N1]
   for (int64_t n = 0; n < N1; ++n) if (onC[n] != n) return false;
   int64_t U = N1;
   for (int64_t n = 1; n < N1; ++n) if (onB[n] != onB[0] + n) { U = n; break; }
@@ -615,22 +623,22 @@ static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_
   for (int64_t n = 0; n < N1; ++n) if (onB[n] != (n / U) * ldXq + n % U) return false;
   const int64_t ldE = okA[1] - okA[0], ldXk = okB[1] - okB[0];
   for (int64_t k = 0; k < a.K; ++k) if (okA[k] != k * ldE || okB[k] != k * ldXk) return false;
-  if (ldE < ZM || b.M != U || b.K != (int64_t)ZM * Q) return false;
+  if (ldE < zm || b.M != U || b.K != (int64_t)zm * Q) return false;
   const int32_t *omA2 = T + b.t.omA, *okA2 = T + b.t.okA, *onB2 = T + b.t.onB, *okB2 = T + b.t.okB, *omC2 = T + b.t.omC, *onC2 = T + b.t.onC;
   for (int64_t u = 0; u < U; ++u) if (omA2[u] != u) return false;                                   // T dense along u
-  for (int i = 0; i < ZM; ++i) if (onB2[i] != i || onC2[i] != i) return false;
-  const int64_t ldC = U > 1 ? omC2[1] - omC2[0] : ZM;
+  for (int i = 0; i < zm; ++i) if (onB2[i] != i || onC2[i] != i) return false;
+  const int64_t ldC = U > 1 ? omC2[1] - omC2[0] : zm;
   for (int64_t u = 0; u < U; ++u) if (omC2[u] != u * ldC) return false;
-  if (ldC < ZM) return false;
+  if (ldC < zm) return false;
   // the contracted group of the second step enumerates (m1, q) in some order: read each entry's (m1, q) off T's offset
   int64_t ldYm = -1, ldYq = Q > 1 ? -1 : 0;
   for (int64_t k = 0; k < b.K; ++k) {
     const int64_t off = okA2[k], m1 = off / N1, q = (off % N1) / U;
-    if (off % U != 0 || m1 >= ZM) return false;
+    if (off % U != 0 || m1 >= zm) return false;
     if (m1 == 1 && q == 0) ldYm = okB2[k];
     if (m1 == 0 && q == 1) ldYq = okB2[k];
   }
-  if (ldYm < ZM || ldYq < 0) return false;
+  if (ldYm < zm || ldYq < 0) return false;
   std::vector<char> seen((size_t)b.K, 0);
   for (int64_t k = 0; k < b.K; ++k) {
     const int64_t off = okA2[k], m1 = off / N1, q = (off % N1) / U;
@@ -1007,7 +1015,8 @@ static int exec_launch_steps(Exec* E) {
       if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
       // the fused pair: 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256):
       // an fp64 step with 128 tile columns reads as k_mfma_f64_g
-      E->launched_tile[s] = (512 << 16) | ((zd.zu == 64 && !zd.f64) ? 128 : 256);
+      // k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a wave sums
+      E->launched_tile[s] = (512 << 16) | (zd.zm == Z1M ? 64 : (zd.zu == 64 && !zd.f64) ? 128 : 256);
       const int per = zd.U / zd.zu;
       if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
         const size_t need = (size_t)per * R;
@@ -1020,6 +1029,7 @@ static int exec_launch_steps(Exec* E) {
         HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
       }
       if (zd.f64) hipLaunchKernelGGL(k_zip_f64, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
+      else if (zd.zm == Z1M) hipLaunchKernelGGL(k_zip128_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       else if (zd.zu == 64) hipLaunchKernelGGL(k_zip64_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       else hipLaunchKernelGGL(k_zip_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       if (E->eager_rescale && P.stabilize && s + 1 < P.n_steps) {
@@ -1801,6 +1811,16 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       if (m128 && (E.sw.zip == 1 || f128 >= 0.9 || f128 >= f64)) { ok = true; z = z128; z.zu = ZU; }
       else if (m64 && (E.sw.zip == 2 || f64 >= 0.9)) { ok = true; z = z64; z.zu = Z6U; }
       else if (m128) { ok = true; z = z128; z.zu = ZU; }
+      // bond 128 (k_zip128_f32: 128 values of u per workgroup, K1 a multiple of its tile depth and two tiles at least -
+      // ZK = Z1K, as zip_match checks), when no bond-256 form matches: only on request (CTN_ZIP=1, and not CTN_ZIP128=0).
+      // kZip128Default is where the rule of the other forms - at least one round of workgroups, rounds filled to 0.9 - would switch it on unasked;
+      // the measurement that has to decide that is in DESIGN section 10.
+      static_assert(Z1K == ZK, "zip_match checks K1 against ZK; k_zip128_f32's tile depth must be the same");
+      if (!m128 && !m64 && E.sw.zip128 != 0 && E.sw.zip != 0 && E.sw.zip != 2 && zip_match(P, s, &z, CTN_F32, Z1U, Z1M) &&
+          z.K1 % Z1K == 0 && z.K1 >= 2 * Z1K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
+          (E.sw.zip == 1 || (kZip128Default && (int64_t)(z.U / Z1U) * replicas >= E.n_cu && fill((int64_t)(z.U / Z1U) * replicas) >= 0.9))) {
+        ok = true; z.zu = Z1U; z.zm = Z1M;
+      }
       if (!ok || z.U / z.zu > kMaxPartials) continue;    // (one abs-sum partial per workgroup: the consumers add at most that many)
       E.zip[s] = z;
       E.zip_skip[s - 1] = 1;

@@ -170,8 +170,13 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                  never exists in memory reports 0.0 and the NEXT launched step carries the product of both:
  *                    - ctn_step_info.kernel == CTN_KERNEL_FUSED (formed inside its consumer);
  *                    - the first step of a zipper pair run as one launch, in every form of it - k_zip_f32,
- *                      k_zip64_f32, k_zip_lat (fp32) and k_zip_f64 (fp64) - (ctn_exec_step_tile reports (1, 1) for
- *                      it): (T / s) Y = (T Y) / s, the second step's factor is s_T * s_E' of the reference;
+ *                      k_zip64_f32, k_zip128_f32, k_zip_lat (fp32) and k_zip_f64 (fp64) - (ctn_exec_step_tile
+ *                      reports (1, 1) for it): (T / s) Y = (T Y) / s, the second step's factor is s_T * s_E' of the
+ *                      reference.  k_zip_lat's factors are BOUNDS: its result leaves as 256 / MP slabs and the pair
+ *                      reports sum over slabs of sum |slab| / numel >= sum |E'| / numel (the true mean within the
+ *                      number of slabs, 4 or 8) unless k_zip_slab_sum runs behind it; the step that consumes the
+ *                      slabs divides by the same number, so the product of all factors is still the reference's
+ *                      (the log register to rounding, 1e-4 in the tests), the individual factors are not;
  *                  the members of a sweep (k_sweep_f32, tile (1, 1) as well) DO report the reference's per-step
  *                  factors, reconstructed after the launch (within 2e-5 relative, fp32).
  */
