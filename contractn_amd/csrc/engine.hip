@@ -38,6 +38,7 @@
 #include "kernels_zip_f64.h"
 #include "kernels_zipl.h"
 #include "kernels_sweep.h"
+#include "kernels_sweep_f64.h"
 #include "kernels_mfma_lat.h"
 #include "kernels_stream.h"
 #include "kernels_grad.h"
@@ -67,6 +68,8 @@ struct DevSwitches {
   int lat = -1;          // CTN_LAT: 0 never use the one-launch latency form (k_mfma_f32_lat), 1 whenever the shape allows (tests)
   int hform = -1;        // CTN_H: 0 never use the one-tile-per-CU form (k_mfma_f32_h), 1 whenever the shape allows (tests)
   int sweep = -1;        // CTN_SWEEP: 0 never walk a chain of epilogue-summed steps in one launch (k_sweep_f32), 1 whenever one matches (tests)
+  int sweep64 = 1;       // CTN_SWEEP64=0: never the float64 sweep (k_sweep_f64), which CTN_SWEEP=1 takes on a float64 plan whose
+                         // per-site step pairs (a GEMM and the streaming sum over p) match
   int dot_tr = 1;        // CTN_DOT_TR=0: full dots against a transposed tensor stay on k_dot_split's 4-byte gathers
   int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches
                          // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
@@ -111,6 +114,7 @@ static DevSwitches read_dev_switches() {
   d.g_big_min_k = num("CTN_G_BIG_MIN_K", 1024);
   d.dot_tr = num("CTN_DOT_TR", 1);
   d.sweep = num("CTN_SWEEP", -1);
+  d.sweep64 = num("CTN_SWEEP64", 1);
   d.lat64_min_k = num("CTN_LAT64_MIN_K", 512);
   d.splitk_fill_long = num("CTN_SPLITK_FILL_LONG", 2);
   d.lat_max_t = num("CTN_LAT_MAX_T", 64);
@@ -182,6 +186,11 @@ struct Exec {
     std::vector<int> steps;          // the members' step indices, in chain order
     int64_t ldIn = 0, ldOut = 0, ldWl = 0, ldWp = 0, ldX = 0;
     int J = 0, M = 0, D = 0, Pd = 0;     // row blocks, rows, bond and physical dimension
+    // float64 (kernels_sweep_f64.h): the members are the 2 S steps of S sites - (GEMM, streaming sum over p) pairs, both
+    // reporting a rescale factor; ids = [S][2] tensor ids (W_s, x_s), idIn the chain's input E
+    bool f64 = false;
+    int idIn = -1;
+    std::vector<int32_t> ids;
   };
   SweepDesc sweep;
   std::vector<char> sweep_role;
@@ -193,6 +202,7 @@ struct Exec {
   double* d_sweep_z = nullptr;         // [R][S]
   double* d_sweep_la = nullptr;        // [R][S][J] logs of d_sweep_a / d_sweep_s
   double* d_sweep_ls = nullptr;
+  int32_t* d_sweep_e = nullptr;        // float64: [R][S][J] exponents of the blocks' scales (d_sweep_a: [R][2 S][J], d_sweep_z: [R][2 S])
   // steps with a small resident left operand against a very wide right one (kernels_mfma_ares.h): column tiles per workgroup
   // (bit 16: the left operand takes 16-byte loads), 0 = not taken
   std::vector<int> ares_ntw;
@@ -260,7 +270,7 @@ struct Exec {
                     (void*)d_log, (void*)d_resc, (void*)d_logs, (void*)d_chain, d_ones, (void*)d_stepP, (void*)d_stepNumel,
                     (void*)d_stepOff, (void*)d_stepSlots,
                     (void*)d_stage_in, (void*)d_stage_out, (void*)d_group_args, (void*)d_sweep_ids, (void*)d_sweep_off,
-                    (void*)d_sweep_slots, (void*)d_sweep_a, (void*)d_sweep_s, (void*)d_sweep_z, (void*)d_sweep_la, (void*)d_sweep_ls,
+                    (void*)d_sweep_slots, (void*)d_sweep_a, (void*)d_sweep_s, (void*)d_sweep_z, (void*)d_sweep_la, (void*)d_sweep_ls, (void*)d_sweep_e,
                     (void*)d_merge, (void*)d_zl_slab[0], (void*)d_zl_slab[1], (void*)d_mult})
       if (p) (void)hipFree(p);
     if (h_pack) (void)hipHostFree(h_pack);
@@ -740,6 +750,102 @@ static bool sweep_match(const Plan& P, Exec::SweepDesc* d) {
   return true;
 }
 
+// Is k_sweep_f64 taken without CTN_SWEEP=1?  Decided by measurement.
+static constexpr bool kSweepF64Default = false;
+
+// The float64 plan keeps a site as TWO steps (plan.cpp fuses them for fp32 only): sa a GEMM of E[b, l] with a network
+// input W carrying {l, p, r}, sb the streaming step that sums p against a network input x[b, p].  Can k_sweep_f64 take
+// the pair as one site?  Matched on the tensors' labels, dims and strides: E and E' row-major [b][.], r unit-stride in W,
+// p unit-stride in x, every stride even (16-byte accesses).  The layout the planner gave C does not matter: C is never
+// written.
+struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
+static bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh) {
+  if (P.dtype != CTN_F64 || sb + 1 >= P.n_steps) return false;              // a step must follow the last member
+  const Step& a = P.steps[sa];
+  const Step& b = P.steps[sb];
+  if (a.kernel != CTN_KERNEL_MFMA_F64 || b.kernel != CTN_KERNEL_ELEMENT || a.rhs < 0 || b.rhs < 0 || a.lhs2 >= 0 || b.lhs2 >= 0 ||
+      a.epw || b.epw)
+    return false;
+  auto axis = [](const Tensor& t, int32_t lab) {
+    int found = -1;
+    for (size_t i = 0; i < t.labels.size(); ++i)
+      if (t.labels[i] == lab) { if (found >= 0) return -1; found = (int)i; }   // (a repeated label: no)
+    return found;
+  };
+  const int idW = P.tensors[a.lhs].labels.size() == 3 ? a.lhs : a.rhs, idE = idW == a.lhs ? a.rhs : a.lhs;
+  if (b.lhs != a.out && b.rhs != a.out) return false;
+  const int idX = b.lhs == a.out ? b.rhs : b.lhs;
+  if (idW >= P.n_inputs || idX >= P.n_inputs || idE == idW) return false;    // W, x: network inputs
+  const Tensor &tE = P.tensors[idE], &tW = P.tensors[idW], &tX = P.tensors[idX], &tC = P.tensors[a.out], &tO = P.tensors[b.out];
+  if (tE.labels.size() != 2 || tW.labels.size() != 3 || tX.labels.size() != 2 || tC.labels.size() != 3 || tO.labels.size() != 2) return false;
+  const int el = axis(tW, tE.labels[0]) >= 0 ? 0 : 1;                        // E = {b, l}: l is the label W carries
+  const int32_t ll = tE.labels[el], lb = tE.labels[1 - el];
+  if (ll == lb || axis(tW, ll) < 0 || axis(tW, lb) >= 0 || axis(tX, lb) < 0) return false;
+  const int32_t lp = tX.labels[1 - axis(tX, lb)];
+  if (lp == lb || lp == ll || axis(tW, lp) < 0) return false;
+  const int32_t lr = tW.labels[3 - axis(tW, ll) - axis(tW, lp)];
+  if (lr == ll || lr == lp || lr == lb) return false;
+  if (axis(tC, lb) < 0 || axis(tC, lp) < 0 || axis(tC, lr) < 0 || axis(tO, lb) < 0 || axis(tO, lr) < 0) return false;
+  const int64_t D = tE.dims[el], Pd = tW.dims[axis(tW, lp)], M = tE.dims[1 - el];
+  if ((D != 64 && D != 128 && D != 256 && D != 512) || (Pd != 2 && Pd != 4) || tW.dims[axis(tW, lr)] != D || M >= ((int64_t)1 << 31) - SWR)
+    return false;
+  if (tE.strides[el] != 1 || tW.strides[axis(tW, lr)] != 1 || tX.strides[axis(tX, lp)] != 1 || tO.strides[axis(tO, lr)] != 1) return false;
+  const int64_t ldA = tE.strides[1 - el], ldC = tO.strides[axis(tO, lb)], ldX = tX.strides[axis(tX, lb)];
+  const int64_t ldWl = tW.strides[axis(tW, ll)], ldWp = tW.strides[axis(tW, lp)];
+  if (ldA < D || ldC < D || ldX < Pd || ldWl <= 0 || ldWp <= 0 || ((ldA | ldC | ldX | ldWl | ldWp) & 1)) return false;
+  if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;   // a lane's offsets into a core: 32 bits, in bytes
+  sh->idE = idE; sh->idW = idW; sh->idX = idX; sh->idOut = b.out;
+  sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = (int)D; sh->Pd = (int)Pd;
+  return true;
+}
+
+// The longest run of such pairs, each taking the result of the one before as its E.  The two safety rules are those of
+// sweep_match: nothing that is launched may lie between two members, and the run's result may overlap its input only as
+// the same region with the same row stride.
+static bool sweep64_match(const Plan& P, Exec::SweepDesc* d) {
+  auto next_launched = [&](int s) { do ++s; while (s < P.n_steps && P.steps[s].kernel == CTN_KERNEL_FUSED); return s; };
+  std::vector<int> best;
+  std::vector<int32_t> best_ids;
+  Sweep64Site best_first, best_last;
+  std::vector<char> used((size_t)P.n_steps, 0);
+  for (int s0 = 0; s0 < P.n_steps; ++s0) {
+    Sweep64Site first, cur, last;
+    int sb = next_launched(s0);
+    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first)) continue;
+    std::vector<int> run{s0, sb};
+    std::vector<int32_t> ids{first.idW, first.idX};
+    last = first;
+    for (;;) {
+      const int na = next_launched(run.back());
+      const int nb = na < P.n_steps ? next_launched(na) : na;
+      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
+          cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC)
+        break;
+      run.push_back(na); run.push_back(nb);
+      ids.push_back(cur.idW); ids.push_back(cur.idX);
+      last = cur;
+    }
+    for (int s : run) used[s] = 1;
+    if (run.size() > best.size()) { best = run; best_ids = ids; best_first = first; best_last = last; }
+  }
+  if (best.size() < 4) return false;            // at least 2 sites
+  {
+    const int idIn = best_first.idE, idOut = best_last.idOut;
+    const bool in_ws = idIn >= P.n_inputs, out_ws = idOut < P.n_inputs + P.n_steps - 1;
+    if (in_ws && out_ws) {
+      const int64_t es = P.elem_size();
+      const int64_t a0 = P.tensors[idIn].ws_offset, a1 = a0 + ((best_first.M - 1) * best_first.ldA + best_first.D) * es;
+      const int64_t b0 = P.tensors[idOut].ws_offset, b1 = b0 + ((best_first.M - 1) * best_last.ldC + best_first.D) * es;
+      const bool overlap = a0 < b1 && b0 < a1;
+      if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
+    }
+  }
+  d->on = true; d->f64 = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
+  d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
+  d->J = (int)((best_first.M + SWR - 1) / SWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
+  return true;
+}
+
 // Is this split dot step the sum over k = (a, b) of X[a Kb + b] Y[b ldY + a] - one operand contiguous in k, the other
 // one its transpose (k_dot_tr)?  Checked on the plan's k tables.
 static bool dot_tr_match(const Plan& P, const Step& st, Exec::DotTr* d) {
@@ -857,6 +963,45 @@ static int exec_launch_steps(Exec* E) {
       if (timed_w) HIPCHECK(hipEventRecord(E->events[ew], E->stream));
       if (E->sweep_role[s] == 1) {
         E->launched_tile[s] = (1 << 16) | 1;        // marker: absorbed into the next launched step
+      } else if (E->sweep.f64) {                    // the last member of a float64 sweep: 2 S member steps, S sites
+        const Exec::SweepDesc& sd = E->sweep;
+        const int S = (int)sd.steps.size() / 2;
+        Sweep64Args w{};
+        w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
+        w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M;
+        w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
+        w.partIn = nullptr; w.PIn = 0; w.strideIn = 0; w.numelIn = 1.0;
+        if (sd.idIn >= P.n_inputs && P.stabilize && P.steps[P.tensors[sd.idIn].producer].kernel != CTN_KERNEL_FUSED) {
+          const int ps = P.tensors[sd.idIn].producer;
+          w.partIn = E->d_partials + (size_t)E->step_off[ps] * R;
+          w.PIn = w.strideIn = E->step_partials[ps];
+          w.numelIn = (double)P.tensors[sd.idIn].numel;
+        }
+        w.min_norm = P.min_norm;
+        w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
+        E->launched_tile[s] = (SWR << 16) | (sd.D * sd.Pd);   // 16 rows x all columns of C per workgroup, every site
+        {
+          const dim3 gs((unsigned)sd.J, (unsigned)R);
+#define CTN_SWEEP64_LAUNCH(DD)                                                                                              \
+          do {                                                                                                              \
+            if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_f64<DD, 4>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);      \
+            else hipLaunchKernelGGL((k_sweep_f64<DD, 2>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);                 \
+          } while (0)
+          if (sd.D == 64) CTN_SWEEP64_LAUNCH(64);
+          else if (sd.D == 128) CTN_SWEEP64_LAUNCH(128);
+          else if (sd.D == 256) CTN_SWEEP64_LAUNCH(256);
+          else CTN_SWEEP64_LAUNCH(512);
+#undef CTN_SWEEP64_LAUNCH
+        }
+        const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
+        hipLaunchKernelGGL(k_sweep64_z, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
+                           (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
+        Sweep64Finish f{};
+        f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+        f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
+        f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
+        f.min_norm = P.stabilize ? P.min_norm : INFINITY;
+        hipLaunchKernelGGL(k_sweep64_finish, dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
       } else {                                      // the last member: the whole chain, then its scale bookkeeping
         const Exec::SweepDesc& sd = E->sweep;
         const int S = (int)sd.steps.size();
@@ -1920,6 +2065,29 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       HIPCHECK_X(hipMalloc((void**)&E.d_sweep_z, (size_t)replicas * S * 8));
       HIPCHECK_X(hipMalloc((void**)&E.d_sweep_la, nrec * 8));
       HIPCHECK_X(hipMalloc((void**)&E.d_sweep_ls, nrec * 8));
+    } else if (P.dtype == CTN_F64 && E.sw.sweep64 != 0 && (E.sw.sweep == 1 || kSweepF64Default) && sweep64_match(P, &sd) &&
+               (int)sd.steps.size() <= 2 * kSweepMaxSites) {
+      // float64 (k_sweep_f64): the run's 2 S steps are all members - a GEMM and a streaming step per site
+      E.sweep = sd;
+      const int T = (int)sd.steps.size(), S = T / 2;
+      E.sweep_role.assign(P.n_steps, 0);
+      std::vector<int32_t> slots((size_t)T);
+      std::vector<int64_t> offs((size_t)T);
+      for (int i = 0; i < T; ++i) {
+        const int s = sd.steps[i];
+        E.sweep_role[s] = i + 1 == T ? 2 : 1;
+        offs[i] = E.step_off[s]; slots[i] = E.step_partials[s];
+      }
+      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_ids, sd.ids.size() * 4));
+      HIPCHECK_X(hipMemcpy(E.d_sweep_ids, sd.ids.data(), sd.ids.size() * 4, hipMemcpyHostToDevice));
+      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_off, offs.size() * 8));
+      HIPCHECK_X(hipMemcpy(E.d_sweep_off, offs.data(), offs.size() * 8, hipMemcpyHostToDevice));
+      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_slots, slots.size() * 4));
+      HIPCHECK_X(hipMemcpy(E.d_sweep_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+      const size_t nrec = (size_t)replicas * S * sd.J;
+      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_a, 2 * nrec * 8));
+      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_e, nrec * 4));
+      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_z, (size_t)replicas * T * 8));
     }
   }
   // leaf groups: runs of consecutive plain streaming steps on network inputs, same kernel variant (see Exec::LeafGroup)

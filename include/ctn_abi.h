@@ -178,7 +178,11 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                      slabs divides by the same number, so the product of all factors is still the reference's
  *                      (the log register to rounding, 1e-4 in the tests), the individual factors are not;
  *                  the members of a sweep (k_sweep_f32, tile (1, 1) as well) DO report the reference's per-step
- *                  factors, reconstructed after the launch (within 2e-5 relative, fp32).
+ *                  factors, reconstructed after the launch (within 2e-5 relative, fp32).  A float64 plan keeps a site of
+ *                  such a chain as TWO steps - the GEMM `bl,plr->bpr` and the streaming sum `bpr,bp->br` - and when
+ *                  k_sweep_f64 walks it (CTN_SWEEP=1) BOTH are members: two entries per site, each the reference's own
+ *                  factor of that step (tile (1, 1) for all but the last member, (16, D P) for the last), reconstructed
+ *                  from the row blocks' abs-sums of C and of E' and their power-of-two scales.
  */
 int ctn_exec_run(ctn_exec* exec, const void* const* inputs, int inputs_space,
                  void* const* outs, int outs_space, double* log_scale, double* step_rescales);
