@@ -35,6 +35,7 @@
 #include "kernels_zip.h"
 #include "kernels_zip64.h"
 #include "kernels_zip128.h"
+#include "kernels_zipm64.h"
 #include "kernels_zip_f64.h"
 #include "kernels_zipl.h"
 #include "kernels_sweep.h"
@@ -76,6 +77,8 @@ struct DevSwitches {
                          // (k_zip_f64) whenever the pair matches; 2 has no fp64 meaning and keeps the two-launch path
   int zip128 = 1;        // CTN_ZIP128=0: never the bond-128 pair kernel (k_zip128_f32), which CTN_ZIP=1 takes for fp32 pairs with
                          // |m1| = |n2| = 128 that no bond-256 form matches
+  int zipm64 = 1;        // CTN_ZIPM64=0: never the bond-64 pair kernel (k_zipm64_f32), which CTN_ZIP=1 takes for fp32 pairs with
+                         // |m1| = |n2| = 64 (no bond-256 and no bond-128 form matches those)
   int zipl = -1;         // CTN_ZIPL: 0 never run a zipper pair as one latency-form launch (k_zip_lat), 1 whenever the pair matches (tests)
   int zipl_max_r = 8;    // CTN_ZIPL_MAX_R: most networks in flight for which k_zip_lat is taken by default (100-site D = 256
                          // network, ms per pass, k_zip_lat / per-step launches: R = 1 1.40 / 2.05, 2: 1.58 / 3.3, 4: 2.1 / 3.5,
@@ -104,6 +107,7 @@ static DevSwitches read_dev_switches() {
   d.hform = num("CTN_H", -1);
   d.zip = num("CTN_ZIP", -1);
   d.zip128 = num("CTN_ZIP128", 1);
+  d.zipm64 = num("CTN_ZIPM64", 1);
   d.zipl = num("CTN_ZIPL", -1);
   d.zipl_max_r = num("CTN_ZIPL_MAX_R", 8);
   d.zipl_mp = num("CTN_ZIPL_MP", 0);
@@ -169,7 +173,7 @@ struct Exec {
   // step of such a pair is never launched (its result only exists in the fused kernel's registers)
   struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
                    int zu = 128; bool f64 = false;      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
-                   int zm = 256; };                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128)
+                   int zm = 256; };                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
   std::vector<ZipDesc> zip;
   std::vector<char> zip_skip;
   // the same pairs in their latency form (kernels_zipl.h): zl[s2] = the fused launch of steps (s2 - 1, s2), whose result
@@ -601,8 +605,10 @@ static void launch_splitk_reduce(Exec* E, int partials, int R, const StepArgs& a
 static constexpr bool kZipF64Default = false;
 // Is k_zip128_f32 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
 static constexpr bool kZip128Default = false;
+// Is k_zipm64_f32 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
+static constexpr bool kZipM64Default = false;
 
-// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32; `zm` = 128: k_zip128_f32) or k_zip_f64 (CTN_F64)
+// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32; `zm` = 128: k_zip128_f32, 64: k_zipm64_f32) or k_zip_f64 (CTN_F64)
 // can run as one launch?
 // Checked on the plan's own offset tables (every operand dense along its innermost index with uniform strides), so
 // nothing about the network's labels is assumed: T = E . X with |m1| = zm rows from E, columns (q, u) from X;
@@ -1160,8 +1166,10 @@ static int exec_launch_steps(Exec* E) {
       if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
       // the fused pair: 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256):
       // an fp64 step with 128 tile columns reads as k_mfma_f64_g
-      // k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a wave sums
-      E->launched_tile[s] = (512 << 16) | (zd.zm == Z1M ? 64 : (zd.zu == 64 && !zd.f64) ? 128 : 256);
+      // k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a wave sums; k_zipm64_f32 (bond 64) likewise
+      // (256, 32): its 256 threads, 32 values of m1 per wave - a tile no plain form reports (theirs are 16 x 16 or have
+      // 64 columns at least)
+      E->launched_tile[s] = zd.zm == Z4M ? ((256 << 16) | 32) : (512 << 16) | (zd.zm == Z1M ? 64 : (zd.zu == 64 && !zd.f64) ? 128 : 256);
       const int per = zd.U / zd.zu;
       if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
         const size_t need = (size_t)per * R;
@@ -1174,6 +1182,7 @@ static int exec_launch_steps(Exec* E) {
         HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
       }
       if (zd.f64) hipLaunchKernelGGL(k_zip_f64, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
+      else if (zd.zm == Z4M) hipLaunchKernelGGL(k_zipm64_f32, dim3((unsigned)((int64_t)per * R)), dim3(256), 0, E->stream, z);
       else if (zd.zm == Z1M) hipLaunchKernelGGL(k_zip128_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       else if (zd.zu == 64) hipLaunchKernelGGL(k_zip64_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       else hipLaunchKernelGGL(k_zip_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
@@ -1965,6 +1974,15 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
           z.K1 % Z1K == 0 && z.K1 >= 2 * Z1K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
           (E.sw.zip == 1 || (kZip128Default && (int64_t)(z.U / Z1U) * replicas >= E.n_cu && fill((int64_t)(z.U / Z1U) * replicas) >= 0.9))) {
         ok = true; z.zu = Z1U; z.zm = Z1M;
+      }
+      // bond 64 (k_zipm64_f32: 64 values of u per workgroup, the same tile depth), when neither a bond-256 nor the bond-128
+      // form matches: only on request (CTN_ZIP=1, and not CTN_ZIPM64=0).  kZipM64Default as kZip128Default: the
+      // measurement that has to decide it is in DESIGN section 10.
+      static_assert(Z4K == ZK, "zip_match checks K1 against ZK; k_zipm64_f32's tile depth must be the same");
+      if (!ok && E.sw.zipm64 != 0 && E.sw.zip != 0 && E.sw.zip != 2 && zip_match(P, s, &z, CTN_F32, Z4U, Z4M) &&
+          z.K1 % Z4K == 0 && z.K1 >= 2 * Z4K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
+          (E.sw.zip == 1 || (kZipM64Default && (int64_t)(z.U / Z4U) * replicas >= E.n_cu && fill((int64_t)(z.U / Z4U) * replicas) >= 0.9))) {
+        ok = true; z.zu = Z4U; z.zm = Z4M;
       }
       if (!ok || z.U / z.zu > kMaxPartials) continue;    // (one abs-sum partial per workgroup: the consumers add at most that many)
       E.zip[s] = z;

@@ -170,8 +170,10 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                  never exists in memory reports 0.0 and the NEXT launched step carries the product of both:
  *                    - ctn_step_info.kernel == CTN_KERNEL_FUSED (formed inside its consumer);
  *                    - the first step of a zipper pair run as one launch, in every form of it - k_zip_f32,
- *                      k_zip64_f32, k_zip128_f32, k_zip_lat (fp32) and k_zip_f64 (fp64) - (ctn_exec_step_tile
- *                      reports (1, 1) for it): (T / s) Y = (T Y) / s, the second step's factor is s_T * s_E' of the
+ *                      k_zip64_f32, k_zip128_f32, k_zipm64_f32, k_zip_lat (fp32) and k_zip_f64 (fp64) -
+ *                      (ctn_exec_step_tile reports (1, 1) for it, and for the second step the form's own tile:
+ *                      (512, 256), (512, 128), (512, 64) for bond 128 and (256, 32) for bond 64, k_zipm64_f32):
+ *                      (T / s) Y = (T Y) / s, the second step's factor is s_T * s_E' of the
  *                      reference.  k_zip_lat's factors are BOUNDS: its result leaves as 256 / MP slabs and the pair
  *                      reports sum over slabs of sum |slab| / numel >= sum |E'| / numel (the true mean within the
  *                      number of slabs, 4 or 8) unless k_zip_slab_sum runs behind it; the step that consumes the
