@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "plan.h"
+#include "cplx_match.h"
 
 #include "kernel_args.h"
 #include "kernels_mfma.h"
@@ -44,6 +45,7 @@
 #include "kernels_stream.h"
 #include "kernels_grad.h"
 #include "kernels_cplx.h"
+#include "kernels_cmfma.h"
 
 namespace ctn {
 
@@ -79,6 +81,8 @@ struct DevSwitches {
                          // |m1| = |n2| = 128 that no bond-256 form matches
   int zipm64 = 1;        // CTN_ZIPM64=0: never the bond-64 pair kernel (k_zipm64_f32), which CTN_ZIP=1 takes for fp32 pairs with
                          // |m1| = |n2| = 64 (no bond-256 and no bond-128 form matches those)
+  int cplx = -1;         // CTN_CPLX: 1 a complex x complex step pair - the S step and the 4-byte-gather GEMM behind it - runs as one launch
+                         // (k_cmfma_f32) wherever cplx_match takes it; 0 or unset: never (kCplxDefault)
   int zipl = -1;         // CTN_ZIPL: 0 never run a zipper pair as one latency-form launch (k_zip_lat), 1 whenever the pair matches (tests)
   int zipl_max_r = 8;    // CTN_ZIPL_MAX_R: most networks in flight for which k_zip_lat is taken by default (100-site D = 256
                          // network, ms per pass, k_zip_lat / per-step launches: R = 1 1.40 / 2.05, 2: 1.58 / 3.3, 4: 2.1 / 3.5,
@@ -109,6 +113,7 @@ static DevSwitches read_dev_switches() {
   d.zip128 = num("CTN_ZIP128", 1);
   d.zipm64 = num("CTN_ZIPM64", 1);
   d.zipl = num("CTN_ZIPL", -1);
+  d.cplx = num("CTN_CPLX", -1);
   d.zipl_max_r = num("CTN_ZIPL_MAX_R", 8);
   d.zipl_mp = num("CTN_ZIPL_MP", 0);
   d.g_splitk = num("CTN_G_SPLITK", 1);
@@ -183,6 +188,12 @@ struct Exec {
   std::vector<ZipLat> zl;
   std::vector<char> zl_skip;
   float* d_zl_slab[2] = {nullptr, nullptr};   // [R][S][U][ZM] each, ping-pong along the chain
+  // complex x complex step pairs (kernels_cmfma.h): cplx[s] describes the fused launch of step s, a GEMM, with the S step
+  // that produces its operand; cplx_skip[that step] = the S step is never launched (the widened operand only exists in registers).
+  // (CplxDesc: cplx_match.h; its t* fields are offsets of the pair-granular tables inside d_cplx_tabs)
+  std::vector<CplxDesc> cplx;
+  std::vector<char> cplx_skip;
+  int32_t* d_cplx_tabs = nullptr;
   // a sweep (kernels_sweep.h): a run of epilogue-summed GEMM steps, each on the result of the one before, walked by ONE
   // launch at the position of its last member; sweep_role[s] = 1 a member that is never launched, 2 the last member
   struct SweepDesc {
@@ -275,7 +286,7 @@ struct Exec {
                     (void*)d_stepOff, (void*)d_stepSlots,
                     (void*)d_stage_in, (void*)d_stage_out, (void*)d_group_args, (void*)d_sweep_ids, (void*)d_sweep_off,
                     (void*)d_sweep_slots, (void*)d_sweep_a, (void*)d_sweep_s, (void*)d_sweep_z, (void*)d_sweep_la, (void*)d_sweep_ls, (void*)d_sweep_e,
-                    (void*)d_merge, (void*)d_zl_slab[0], (void*)d_zl_slab[1], (void*)d_mult})
+                    (void*)d_merge, (void*)d_zl_slab[0], (void*)d_zl_slab[1], (void*)d_mult, (void*)d_cplx_tabs})
       if (p) (void)hipFree(p);
     if (h_pack) (void)hipHostFree(h_pack);
     if (h_group_args) (void)hipHostFree(h_group_args);
@@ -666,6 +677,11 @@ static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_
   z->Q = (int)Q; z->U = (int)U; z->K1 = (int)a.K;
   return true;
 }
+
+// Is k_cmfma_f32 taken without CTN_CPLX=1 wherever cplx_match takes a pair?  Decided by measurement (DESIGN sections 10
+// and 11): tools/cplx_step_timing.py has to show the fused form ahead of the two launches by more than the larger spread
+// at every one of its shapes, and the complex GPU suite has to be green with CTN_CPLX=1.
+static constexpr bool kCplxDefault = false;
 
 // Is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
 // offset tables: E row-major [b][l], W[l][p][r] with r unit-stride, x[b][p] with p unit-stride, result rows [b][r].
@@ -1199,6 +1215,16 @@ static int exec_launch_steps(Exec* E) {
       if (timed_z) HIPCHECK(hipEventRecord(E->events[ez + 1], E->stream));
       continue;
     }
+    if (!E->cplx_skip.empty() && E->cplx_skip[s]) {   // the S step of a complex pair: runs inside the next step's launch
+      if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
+      E->launched_tile[s] = (1 << 16) | 1;          // marker: absorbed into the next launched step
+      if (E->timing_runs < E->timing_slots) {
+        const size_t e0 = ((size_t)E->timing_runs * P.n_steps + s) * 2;
+        HIPCHECK(hipEventRecord(E->events[e0], E->stream));
+        HIPCHECK(hipEventRecord(E->events[e0 + 1], E->stream));
+      }
+      continue;
+    }
     if (st.kernel == CTN_KERNEL_FUSED) {   // formed on the fly inside its consumer: nothing to launch
       if (E->timing_runs < E->timing_slots) {
         const size_t e0 = ((size_t)E->timing_runs * P.n_steps + s) * 2;
@@ -1267,6 +1293,38 @@ static int exec_launch_steps(Exec* E) {
       case CTN_KERNEL_MFMA_F32: {
         const int64_t total = (int64_t)st.blocks * R;
         if (total >= (1LL << 31)) { g_err = "grid too large"; return CTN_UNSUPPORTED; }
+        if (!E->cplx.empty() && E->cplx[s].on) {
+          // a complex x complex step: the S step before it and this GEMM as one launch (k_cmfma_f32), reading `small`
+          // and `big` as arrays of pairs; the scales are those of `small` (not of the never-written mid) and of `big`
+          const CplxDesc& cd = E->cplx[s];
+          const int32_t* CT = E->d_cplx_tabs;
+          CplxArgs c{};
+          c.txr = CT + cd.txr; c.txk = CT + cd.txk; c.tyn = CT + cd.tyn; c.tyk = CT + cd.tyk; c.tcx = CT + cd.tcx; c.tcy = CT + cd.tcy;
+          c.ptrs = E->d_ptrs;
+          part_of(cd.small, &c.partX, &c.PX, &c.strideX, &c.numelX);
+          part_of(cd.big, &c.partY, &c.PY, &c.strideY, &c.numelY);
+          c.min_norm = P.min_norm;
+          c.Mx = cd.Mx; c.Ny = cd.Ny; c.Kc = cd.Kc;
+          c.idX = cd.small; c.idY = cd.big; c.idS = cd.sid; c.idC = st.out; c.n_tensors = E->n_tensors;
+          c.tiles_x = (cd.Mx + CX_TX - 1) / CX_TX; c.tiles_y = (cd.Ny + CX_TY - 1) / CX_TY;
+          c.blocks_per_replica = c.tiles_x * c.tiles_y; c.R = R;
+          c.sa = cd.sa; c.sb = cd.sb; c.so = cd.so; c.sO = cd.sO; c.legx = cd.legx; c.legy = cd.legy;
+          c.c_vec2 = (cd.cvec2 && (s + 1 < P.n_steps || E->outs_aligned16)) ? 1 : 0;
+          if (c.blocks_per_replica > kMaxPartials) {       // more workgroups than slots: through the collapse pass
+            do_collapse = true; collapse_blocks = c.blocks_per_replica;
+            c.partC = E->d_scratch; c.partC_stride = collapse_blocks;
+          } else {
+            do_collapse = false;
+            c.partC = part_dst; c.partC_stride = part_stride;
+          }
+          used_tile(CX_TX, 2 * CX_TY);   // 64 pairs of `small` x (128 entries of `big` x 2 components): no plain form reports it
+          const dim3 gc((unsigned)((int64_t)c.blocks_per_replica * R));
+          if (cd.kfx && cd.kfy) hipLaunchKernelGGL((k_cmfma_f32<true, true>), gc, dim3(256), 0, E->stream, c);
+          else if (cd.kfx) hipLaunchKernelGGL((k_cmfma_f32<true, false>), gc, dim3(256), 0, E->stream, c);
+          else if (cd.kfy) hipLaunchKernelGGL((k_cmfma_f32<false, true>), gc, dim3(256), 0, E->stream, c);
+          else hipLaunchKernelGGL((k_cmfma_f32<false, false>), gc, dim3(256), 0, E->stream, c);
+          break;
+        }
         if (const int ntw_av = (int)E->ares_ntw.size() == P.n_steps ? E->ares_ntw[s] : 0) {
           const int ntw = ntw_av & 0xffff, avec = ntw_av >> 16;
           // the left operand resident in registers, `ntw` column tiles per workgroup (k_mfma_f32_ares); one partial per
@@ -2037,6 +2095,35 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       E.zl.clear(); E.zl_skip.clear();
     }
   }
+  // complex x complex step pairs (k_cmfma_f32): only on request (CTN_CPLX=1) while kCplxDefault is off
+  if (!P.chain && P.dtype == CTN_F32 && (E.sw.cplx == 1 || (kCplxDefault && E.sw.cplx != 0))) {
+    E.cplx.assign(P.n_steps, CplxDesc());
+    E.cplx_skip.assign(P.n_steps, 0);
+    std::vector<int32_t> tabs;
+    bool any = false;
+    for (int s = 1; s < P.n_steps; ++s) {
+      if ((!E.zip.empty() && (E.zip[s].on || E.zip_skip[s])) || (!E.zl.empty() && (E.zl[s].on || E.zl_skip[s])))
+        continue;      // (a zipper pair is two GEMM steps: its members never have an S step behind them)
+      CplxDesc cd;
+      if (!cplx_match(P, s, &cd, &tabs)) continue;
+      const int64_t tiles = (int64_t)((cd.Mx + CX_TX - 1) / CX_TX) * ((cd.Ny + CX_TY - 1) / CX_TY);
+      E.cplx[s] = cd;
+      E.cplx_skip[cd.sp] = 1;
+      any = true;
+      // one abs-sum partial per workgroup of the fused launch (beyond the slots: collapsed to one); the skipped S step
+      // keeps its (never written, zero) slots: its rescale reads 0.0
+      E.step_partials[s] = tiles > kMaxPartials ? 1 : (int)tiles;
+      scratch_need = std::max<int64_t>(scratch_need, tiles);
+    }
+    if (any) {
+      E.part_slots = 0;
+      for (int s = 0; s < P.n_steps; ++s) { E.step_off[s] = E.part_slots; E.part_slots += E.step_partials[s]; }
+      HIPCHECK_X(hipMalloc((void**)&E.d_cplx_tabs, tabs.size() * 4));
+      HIPCHECK_X(hipMemcpy(E.d_cplx_tabs, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
+    } else {
+      E.cplx.clear(); E.cplx_skip.clear();
+    }
+  }
   // full dots against a transposed tensor
   if (!P.chain && E.sw.dot_tr) {
     E.dot_tr.assign(P.n_steps, Exec::DotTr());
@@ -2114,7 +2201,8 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
     auto leaf = [&](int s, int* vw, int* u) {
       const Step& st = P.steps[s];
       if (st.kernel != CTN_KERNEL_ELEMENT || st.kvec || st.collapse || s + 1 >= P.n_steps || st.rhs < 0 ||
-          st.lhs >= P.n_inputs || st.rhs >= P.n_inputs || st.lhs2 >= 0 || stream_splits(st, replicas, E.n_cu))
+          st.lhs >= P.n_inputs || st.rhs >= P.n_inputs || st.lhs2 >= 0 || stream_splits(st, replicas, E.n_cu) ||
+          (!E.cplx_skip.empty() && E.cplx_skip[s]))      // (the S step of a complex pair is never launched)
         return false;
       int64_t nq;
       *vw = st.vecw;
@@ -2256,6 +2344,7 @@ static bool exec_scales_suspect(const Exec* E, const double* resc = nullptr, int
       if (st.kernel == CTN_KERNEL_FUSED) continue;
       if (!E->zip_skip.empty() && E->zip_skip[s]) continue;          // runs inside the next step's launch
       if (!E->zl_skip.empty() && E->zl_skip[s]) continue;
+      if (!E->cplx_skip.empty() && E->cplx_skip[s]) continue;
       if (!E->sweep_role.empty() && E->sweep_role[s] && !E->eager_rescale) {   // a sweep keeps its products in range by itself
         if (!std::isfinite(rs[s])) return true;
         continue;
@@ -2263,6 +2352,8 @@ static bool exec_scales_suspect(const Exec* E, const double* resc = nullptr, int
       double sab = scale_of(st.lhs) * (st.rhs >= 0 ? scale_of(st.rhs) : 1.0) * (st.lhs2 >= 0 ? scale_of(st.lhs2) : 1.0);
       if ((!E->zip.empty() && E->zip[s].on) || (!E->zl.empty() && E->zl[s].on))   // the fused pair accumulates on E, X and Y as stored
         sab = scale_of(P.steps[s - 1].lhs) * scale_of(P.steps[s - 1].rhs) * scale_of(st.rhs);
+      if (!E->cplx.empty() && E->cplx[s].on)                         // the complex pair accumulates on `small` and `big` as stored
+        sab = scale_of(E->cplx[s].small) * scale_of(E->cplx[s].big);
       const double so = rs[s];
       if (!std::isfinite(so) || !std::isfinite(sab)) return true;
       if (so == 0.0) { if (sab > zhi || sab < zlo) return true; continue; }

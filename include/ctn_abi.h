@@ -179,6 +179,11 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                      number of slabs, 4 or 8) unless k_zip_slab_sum runs behind it; the step that consumes the
  *                      slabs divides by the same number, so the product of all factors is still the reference's
  *                      (the log register to rounding, 1e-4 in the tests), the individual factors are not;
+ *                    - the S step of a complex x complex step run as one launch (k_cmfma_f32, CTN_CPLX=1: the
+ *                      streaming step that contracts the 2 x 2 x 2 structure tensor into the smaller operand, and the
+ *                      GEMM that is the only consumer of its result): the widened operand never exists, the S step
+ *                      reports 0.0 and tile (1, 1), the GEMM step the tile (64, 256) - 64 pairs of the smaller operand
+ *                      by 128 entries of the other one's free group, both components - and the product of both factors;
  *                  the members of a sweep (k_sweep_f32, tile (1, 1) as well) DO report the reference's per-step
  *                  factors, reconstructed after the launch (within 2e-5 relative, fp32).  A float64 plan keeps a site of
  *                  such a chain as TWO steps - the GEMM `bl,plr->bpr` and the streaming sum `bpr,bp->br` - and when
@@ -275,6 +280,9 @@ int ctn_exec_merge_scales(ctn_exec* exec, int t_dtype, void* buf, int64_t stride
  * (0, 0 for non-MFMA steps or before the first enqueue).  The planner's choice (ctn_step_info.tile_m/n)
  * can be overridden at launch time by the number of replicas: few tiles -> 64 x 64 split-K or 128 x 64,
  * many full long-K tiles -> 256 x 256.  Measurement tooling only (bench.py keys its per-kernel roofline on it).
+ * A step that runs inside the launch of a later one (see step_rescales above) reports (1, 1); the fused forms report
+ * tiles no plain form has: the zipper pairs (512, 256), (512, 128), (512, 64), (256, 32), (32, 256), (64, 256 with
+ * (1, 1) before it); a sweep (16, D P); the complex pair k_cmfma_f32 (64, 256) behind the (1, 1) of its S step.
  */
 int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t* tile_n);
 
