@@ -34,6 +34,7 @@
 #include "kernels_mfma_h.h"
 #include "kernels_mfma_ares.h"
 #include "kernels_zip.h"
+#include "kernels_zipq.h"
 #include "kernels_zip64.h"
 #include "kernels_zip128.h"
 #include "kernels_zipm64.h"
@@ -77,6 +78,8 @@ struct DevSwitches {
   int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches
                          // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
                          // (k_zip_f64) whenever the pair matches; 2 has no fp64 meaning and keeps the two-launch path
+  int zipq = -1;         // CTN_ZIPQ: 0 never the two-legs-per-pass form of the bond-256 pair (k_zipq_f32), 1 whenever the pair matches it
+                         // (zip_match and Q even - tests), unset: kZipQDefault where k_zip_f32 is taken by its own default rule
   int zip128 = 1;        // CTN_ZIP128=0: never the bond-128 pair kernel (k_zip128_f32), which CTN_ZIP=1 takes for fp32 pairs with
                          // |m1| = |n2| = 128 that no bond-256 form matches
   int zipm64 = 1;        // CTN_ZIPM64=0: never the bond-64 pair kernel (k_zipm64_f32), which CTN_ZIP=1 takes for fp32 pairs with
@@ -110,6 +113,7 @@ static DevSwitches read_dev_switches() {
   d.lat = num("CTN_LAT", -1);
   d.hform = num("CTN_H", -1);
   d.zip = num("CTN_ZIP", -1);
+  d.zipq = num("CTN_ZIPQ", -1);
   d.zip128 = num("CTN_ZIP128", 1);
   d.zipm64 = num("CTN_ZIPM64", 1);
   d.zipl = num("CTN_ZIPL", -1);
@@ -178,7 +182,8 @@ struct Exec {
   // step of such a pair is never launched (its result only exists in the fused kernel's registers)
   struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
                    int zu = 128; bool f64 = false;      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
-                   int zm = 256; };                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
+                   int zm = 256;
+                   bool zq = false; };                  // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even)                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
   std::vector<ZipDesc> zip;
   std::vector<char> zip_skip;
   // the same pairs in their latency form (kernels_zipl.h): zl[s2] = the fused launch of steps (s2 - 1, s2), whose result
@@ -224,6 +229,7 @@ struct Exec {
   // full dots of a tensor with a transposed one (k_dot_tr), found on the plan's tables when the executor is created
   struct DotTr { bool on = false; int Ka = 0, Kb = 0, x_is_a = 1; int64_t ldY = 0; };
   std::vector<DotTr> dot_tr;
+  std::vector<int32_t> launched_form;  // per step: ctn_step_form of the last enqueue (ctn_exec_step_form), else 0
   std::vector<int32_t> launched_tile;  // per step: (tile rows << 16 | tile columns) of the last enqueue's MFMA kernel, else 0
   char* d_ws = nullptr;
   int32_t* d_tables = nullptr;
@@ -676,6 +682,18 @@ static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_
   z->on = true; z->f64 = f64; z->ldE = ldE; z->ldXq = ldXq; z->ldXk = ldXk; z->ldYq = ldYq; z->ldYm = ldYm; z->ldC = ldC;
   z->Q = (int)Q; z->U = (int)U; z->K1 = (int)a.K;
   return true;
+}
+
+// Is k_zipq_f32 taken without CTN_ZIPQ=1 where k_zip_f32 would be by its own default rule (fp32, one round of workgroups at
+// least, rounds filled)?  Decided by measurement: +3.3 % on the headline at R = 512, +3.0 % at 128, +3.1 % at 256,
+// fourteen times the larger spread.
+static constexpr bool kZipQDefault = true;
+// Can k_zipq_f32 run a pair that zip_match took for k_zip_f32?  Its legs go in pairs, and its LDS-DMA requests address
+// every operand with an unsigned 32-bit byte offset off the tensor's base.
+static bool zipq_fits(const Exec::ZipDesc& z) {
+  const int64_t lim = (int64_t)1 << 31;
+  return z.Q >= 2 && z.Q % 2 == 0 && (int64_t)z.K1 * z.ldE * 4 < lim && ((int64_t)z.Q * z.ldXq + (int64_t)z.K1 * z.ldXk + z.U) * 4 < lim &&
+         ((int64_t)z.Q * z.ldYq + (int64_t)ZM * z.ldYm) * 4 < lim;
 }
 
 // Is k_cmfma_f32 taken without CTN_CPLX=1 wherever cplx_match takes a pair?  Decided by measurement (DESIGN sections 10
@@ -1180,6 +1198,9 @@ static int exec_launch_steps(Exec* E) {
       const size_t ez = timed_z ? ((size_t)E->timing_runs * P.n_steps + s) * 2 : 0;
       if (timed_z) HIPCHECK(hipEventRecord(E->events[ez], E->stream));
       if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
+      if ((int)E->launched_form.size() != P.n_steps) E->launched_form.assign(P.n_steps, 0);
+      E->launched_form[s] = zd.f64 ? CTN_FORM_ZIP_F64 : zd.zm == Z4M ? CTN_FORM_ZIPM64 : zd.zm == Z1M ? CTN_FORM_ZIP128
+                            : zd.zu == 64 ? CTN_FORM_ZIP64 : zd.zq ? CTN_FORM_ZIPQ : CTN_FORM_ZIP;
       // the fused pair: 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256):
       // an fp64 step with 128 tile columns reads as k_mfma_f64_g
       // k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a wave sums; k_zipm64_f32 (bond 64) likewise
@@ -1201,6 +1222,7 @@ static int exec_launch_steps(Exec* E) {
       else if (zd.zm == Z4M) hipLaunchKernelGGL(k_zipm64_f32, dim3((unsigned)((int64_t)per * R)), dim3(256), 0, E->stream, z);
       else if (zd.zm == Z1M) hipLaunchKernelGGL(k_zip128_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       else if (zd.zu == 64) hipLaunchKernelGGL(k_zip64_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
+      else if (zd.zq) hipLaunchKernelGGL(k_zipq_f32, dim3((unsigned)((int64_t)per * R)), dim3(256), 0, E->stream, z);
       else hipLaunchKernelGGL(k_zip_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       if (E->eager_rescale && P.stabilize && s + 1 < P.n_steps) {
         const int64_t numel = P.tensors[st.out].numel;
@@ -2023,6 +2045,10 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       if (m128 && (E.sw.zip == 1 || f128 >= 0.9 || f128 >= f64)) { ok = true; z = z128; z.zu = ZU; }
       else if (m64 && (E.sw.zip == 2 || f64 >= 0.9)) { ok = true; z = z64; z.zu = Z6U; }
       else if (m128) { ok = true; z = z128; z.zu = ZU; }
+      // the 128-u form with two legs per pass (k_zipq_f32): on request wherever the pair matches (CTN_ZIPQ=1, also where
+      // the rules above chose otherwise - but not against CTN_ZIP=2), else under k_zip_f32's own default rule
+      if (E.sw.zipq == 1 && E.sw.zip != 2 && zip_match(P, s, &z128, CTN_F32) && zipq_fits(z128)) { ok = true; z = z128; z.zu = ZU; z.zq = true; }
+      else if (E.sw.zipq == -1 && kZipQDefault && E.sw.zip == -1 && ok && z.zu == ZU && f128 >= 0.9 && zipq_fits(z)) z.zq = true;
       // bond 128 (k_zip128_f32: 128 values of u per workgroup, K1 a multiple of its tile depth and two tiles at least -
       // ZK = Z1K, as zip_match checks), when no bond-256 form matches: only on request (CTN_ZIP=1, and not CTN_ZIP128=0).
       // kZip128Default is where the rule of the other forms - at least one round of workgroups, rounds filled to 0.9 - would switch it on unasked;
@@ -2659,6 +2685,12 @@ int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t*
   const int32_t v = step < (int)exec->e.launched_tile.size() ? exec->e.launched_tile[step] : 0;
   *tile_m = v >> 16;
   *tile_n = v & 0xFFFF;
+  return CTN_OK;
+}
+
+int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form) {
+  if (!exec || !form || step < 0 || step >= exec->e.plan->n_steps) { g_err = "invalid step query"; return CTN_INVALID_ARG; }
+  *form = step < (int)exec->e.launched_form.size() ? exec->e.launched_form[step] : 0;
   return CTN_OK;
 }
 

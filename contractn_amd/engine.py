@@ -37,13 +37,15 @@ ABI_SYMBOLS = (
     "ctn_plan_workspace_bytes", "ctn_plan_step_info",
     "ctn_exec_create", "ctn_exec_destroy", "ctn_exec_run", "ctn_exec_enqueue",
     "ctn_exec_fetch", "ctn_exec_synchronize", "ctn_exec_set_timing", "ctn_exec_step_ms",
-    "ctn_exec_step_tile", "ctn_exec_set_rescale_mode", "ctn_exec_eager_reruns",
+    "ctn_exec_step_tile", "ctn_exec_step_form", "ctn_exec_set_rescale_mode", "ctn_exec_eager_reruns",
     "ctn_exec_snapshot_scales", "ctn_exec_scales_suspect", "ctn_exec_combine_split",
     "ctn_exec_add_scales", "ctn_exec_merge_scales", "ctn_exec_report_suspect",
     "ctn_exec_set_finish_mode", "ctn_exec_finish",
     "ctn_grad_seed", "ctn_grad_leaf",
     "ctn_cplx_normalize", "ctn_cplx_normalize_grad",
 )
+# ctn_step_form (ctn_exec_step_form): the fused zipper-pair kernel a step ran as
+STEP_FORMS = {0: None, 1: "k_zip_f32", 2: "k_zipq_f32", 3: "k_zip64_f32", 4: "k_zip128_f32", 5: "k_zipm64_f32", 6: "k_zip_f64"}
 GRAD_SCRATCH = 512          # doubles of scratch ctn_grad_seed needs (CTN_GRAD_SCRATCH)
 GRAD_MAX_DIMS = 64          # axes of an operand ctn_grad_leaf writes (CTN_GRAD_MAX_DIMS)
 CPLX_SCRATCH = 1024         # doubles of scratch ctn_cplx_normalize(_grad) needs (CTN_CPLX_SCRATCH)
@@ -160,6 +162,7 @@ def load_library():
         "ctn_exec_set_timing": (i32, [vp, i32]),
         "ctn_exec_step_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "ctn_exec_step_tile": (i32, [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "ctn_exec_step_form": (i32, [vp, i32, C.POINTER(C.c_int32)]),
         "ctn_exec_set_rescale_mode": (i32, [vp, i32]),
         "ctn_exec_eager_reruns": (i32, [vp]),
         "ctn_exec_snapshot_scales": (i32, [vp, vp, i32, vp]),
@@ -552,6 +555,15 @@ class Executor:
         for s in range(self.plan.n_steps):
             _check(self._lib.ctn_exec_step_tile(self._h, self.plan.native_step(s), C.byref(tm), C.byref(tn)))
             out.append((tm.value, tn.value))
+        return out
+
+    def step_forms(self):
+        """Per step, which fused zipper-pair kernel the last enqueue launched: a key of `STEP_FORMS` (0 = none)."""
+        out = []
+        form = C.c_int32(0)
+        for s in range(self.plan.n_steps):
+            _check(self._lib.ctn_exec_step_form(self._h, self.plan.native_step(s), C.byref(form)))
+            out.append(form.value)
         return out
 
     def step_ms(self):

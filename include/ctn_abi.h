@@ -287,6 +287,24 @@ int ctn_exec_merge_scales(ctn_exec* exec, int t_dtype, void* buf, int64_t stride
 int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t* tile_n);
 
 /*
+ * Which fused zipper-pair kernel the LAST enqueue launched for `step` (read-only; measurement and tests).  Several forms
+ * report the same tile - k_zip_f32 and k_zipq_f32 both (512, 256), "the 128-u throughput form" - and this tells them
+ * apart.  CTN_FORM_NONE for every step that did not run as the launched (second) step of such a pair, and before the
+ * first enqueue.  (An entry point added to the ABI leaves CTN_ABI_VERSION as it is: the version counts changes a
+ * caller of the earlier entry points has to know about.)
+ */
+typedef enum {
+  CTN_FORM_NONE = 0,
+  CTN_FORM_ZIP = 1,     /* k_zip_f32 */
+  CTN_FORM_ZIPQ = 2,    /* k_zipq_f32: two physical legs per pass over E, one wave per SIMD */
+  CTN_FORM_ZIP64 = 3,   /* k_zip64_f32 */
+  CTN_FORM_ZIP128 = 4,  /* k_zip128_f32 */
+  CTN_FORM_ZIPM64 = 5,  /* k_zipm64_f32 */
+  CTN_FORM_ZIP_F64 = 6  /* k_zip_f64 */
+} ctn_step_form;
+int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form);
+
+/*
  * Per-step device timing with HIP events recorded on the executor's stream.
  * ctn_exec_set_timing(exec, slots): slots > 0 brackets every step's kernels of
  * the next `slots` enqueues with events (later enqueues run without events);
