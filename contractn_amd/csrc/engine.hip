@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "plan.h"
+#include "chain_pack.h"
 #include "cplx_match.h"
 
 #include "kernel_args.h"
@@ -44,6 +45,7 @@
 #include "kernels_sweep_f64.h"
 #include "kernels_mfma_lat.h"
 #include "kernels_stream.h"
+#include "kernels_chain.h"
 #include "kernels_grad.h"
 #include "kernels_cplx.h"
 #include "kernels_cmfma.h"
@@ -86,6 +88,8 @@ struct DevSwitches {
                          // |m1| = |n2| = 64 (no bond-256 and no bond-128 form matches those)
   int cplx = -1;         // CTN_CPLX: 1 a complex x complex step pair - the S step and the 4-byte-gather GEMM behind it - runs as one launch
                          // (k_cmfma_f32) wherever cplx_match takes it; 0 or unset: never (kCplxDefault)
+  int chain = -1;        // CTN_CHAIN: 1 a chain plan is always walked by k_chain, 2 by k_chain_lds (records, inputs and intermediates
+                         // on chip) wherever chain_pack accepts the plan; unset: kChainLdsDefault
   int zipl = -1;         // CTN_ZIPL: 0 never run a zipper pair as one latency-form launch (k_zip_lat), 1 whenever the pair matches (tests)
   int zipl_max_r = 8;    // CTN_ZIPL_MAX_R: most networks in flight for which k_zip_lat is taken by default (100-site D = 256
                          // network, ms per pass, k_zip_lat / per-step launches: R = 1 1.40 / 2.05, 2: 1.58 / 3.3, 4: 2.1 / 3.5,
@@ -118,6 +122,7 @@ static DevSwitches read_dev_switches() {
   d.zipm64 = num("CTN_ZIPM64", 1);
   d.zipl = num("CTN_ZIPL", -1);
   d.cplx = num("CTN_CPLX", -1);
+  d.chain = num("CTN_CHAIN", -1);
   d.zipl_max_r = num("CTN_ZIPL_MAX_R", 8);
   d.zipl_mp = num("CTN_ZIPL_MP", 0);
   d.g_splitk = num("CTN_G_SPLITK", 1);
@@ -250,6 +255,8 @@ struct Exec {
   double* d_resc = nullptr;
   double* d_logs = nullptr;
   ChainStep* d_chain = nullptr;
+  int32_t* d_chain_prog = nullptr;  // k_chain_lds: the packed program (chain_pack.h); null = the plan is walked by k_chain
+  int chain_len0 = 0;               // ... and the length of its first record
   unsigned long long* d_dbg = nullptr;  // CTN_DEBUG_STAMPS=<file>: stamps of the LAST MFMA launch
   size_t dbg_tiles = 0;
   char* h_pack = nullptr;       // pinned host bounce buffer for many-small-operand staging
@@ -292,7 +299,7 @@ struct Exec {
                     (void*)d_stepOff, (void*)d_stepSlots,
                     (void*)d_stage_in, (void*)d_stage_out, (void*)d_group_args, (void*)d_sweep_ids, (void*)d_sweep_off,
                     (void*)d_sweep_slots, (void*)d_sweep_a, (void*)d_sweep_s, (void*)d_sweep_z, (void*)d_sweep_la, (void*)d_sweep_ls, (void*)d_sweep_e,
-                    (void*)d_merge, (void*)d_zl_slab[0], (void*)d_zl_slab[1], (void*)d_mult, (void*)d_cplx_tabs})
+                    (void*)d_merge, (void*)d_zl_slab[0], (void*)d_zl_slab[1], (void*)d_mult, (void*)d_cplx_tabs, (void*)d_chain_prog})
       if (p) (void)hipFree(p);
     if (h_pack) (void)hipHostFree(h_pack);
     if (h_group_args) (void)hipHostFree(h_group_args);
@@ -701,6 +708,11 @@ static bool zipq_fits(const Exec::ZipDesc& z) {
 // at every one of its shapes, and the complex GPU suite has to be green with CTN_CPLX=1.
 static constexpr bool kCplxDefault = false;
 
+// Is a chain plan walked by k_chain_lds without CTN_CHAIN=2 wherever chain_pack accepts it?  Decided by measurement
+// (DESIGN sections 10 and 11): tools/chain_timing.py has to show it ahead of k_chain by more than the larger spread at
+// every workload it measures, and the whole suite has to be green with it on.  Results are bit-identical either way.
+static constexpr bool kChainLdsDefault = false;
+
 // Is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
 // offset tables: E row-major [b][l], W[l][p][r] with r unit-stride, x[b][p] with p unit-stride, result rows [b][r].
 struct SweepShape { int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
@@ -972,7 +984,13 @@ static int exec_launch_steps(Exec* E) {
     if (timed) {
       HIPCHECK(hipEventRecord(E->events[ev0], E->stream));
     }
-    if (P.dtype == CTN_F32)
+    if (E->d_chain_prog && P.dtype == CTN_F32)
+      hipLaunchKernelGGL(k_chain_lds<float>, dim3(R), dim3(256), 0, E->stream, (const int32_t*)E->d_chain_prog, E->chain_len0, P.n_steps,
+                         (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
+    else if (E->d_chain_prog)
+      hipLaunchKernelGGL(k_chain_lds<double>, dim3(R), dim3(256), 0, E->stream, (const int32_t*)E->d_chain_prog, E->chain_len0, P.n_steps,
+                         (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
+    else if (P.dtype == CTN_F32)
       hipLaunchKernelGGL(k_chain<float>, dim3(R), dim3(256), 0, E->stream, (const ChainStep*)E->d_chain, P.n_steps,
                          (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
     else
@@ -2302,6 +2320,16 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
     }
     HIPCHECK_X(hipMalloc((void**)&E.d_chain, cs.size() * sizeof(ChainStep)));
     HIPCHECK_X(hipMemcpy(E.d_chain, cs.data(), cs.size() * sizeof(ChainStep), hipMemcpyHostToDevice));
+    // the on-chip walker, where asked for and where the packer takes the plan (a refusal keeps k_chain)
+    if (E.sw.chain == 2 || (kChainLdsDefault && E.sw.chain != 1)) {
+      ChainProgram cp;
+      std::string why;
+      if (chain_pack(P, &cp, &why)) {
+        HIPCHECK_X(hipMalloc((void**)&E.d_chain_prog, cp.words.size() * 4));
+        HIPCHECK_X(hipMemcpy(E.d_chain_prog, cp.words.data(), cp.words.size() * 4, hipMemcpyHostToDevice));
+        E.chain_len0 = cp.steps[0].len;
+      }
+    }
   }
   // pointer table: intermediates and the ones-scalar are fixed for the executor's lifetime
   E.h_ptrs.assign((size_t)replicas * E.n_tensors, nullptr);
@@ -2691,6 +2719,13 @@ int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t*
 int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form) {
   if (!exec || !form || step < 0 || step >= exec->e.plan->n_steps) { g_err = "invalid step query"; return CTN_INVALID_ARG; }
   *form = step < (int)exec->e.launched_form.size() ? exec->e.launched_form[step] : 0;
+  return CTN_OK;
+}
+
+int ctn_exec_walk_form(const ctn_exec* exec, int32_t* form) {
+  if (!exec || !form) { g_err = "NULL argument"; return CTN_INVALID_ARG; }
+  const Exec& E = exec->e;
+  *form = !(E.plan->chain && E.d_chain) ? CTN_WALK_NONE : E.d_chain_prog ? CTN_WALK_CHAIN_LDS : CTN_WALK_CHAIN;
   return CTN_OK;
 }
 

@@ -37,7 +37,7 @@ ABI_SYMBOLS = (
     "ctn_plan_workspace_bytes", "ctn_plan_step_info",
     "ctn_exec_create", "ctn_exec_destroy", "ctn_exec_run", "ctn_exec_enqueue",
     "ctn_exec_fetch", "ctn_exec_synchronize", "ctn_exec_set_timing", "ctn_exec_step_ms",
-    "ctn_exec_step_tile", "ctn_exec_step_form", "ctn_exec_set_rescale_mode", "ctn_exec_eager_reruns",
+    "ctn_exec_step_tile", "ctn_exec_step_form", "ctn_exec_walk_form", "ctn_exec_set_rescale_mode", "ctn_exec_eager_reruns",
     "ctn_exec_snapshot_scales", "ctn_exec_scales_suspect", "ctn_exec_combine_split",
     "ctn_exec_add_scales", "ctn_exec_merge_scales", "ctn_exec_report_suspect",
     "ctn_exec_set_finish_mode", "ctn_exec_finish",
@@ -46,6 +46,8 @@ ABI_SYMBOLS = (
 )
 # ctn_step_form (ctn_exec_step_form): the fused zipper-pair kernel a step ran as
 STEP_FORMS = {0: None, 1: "k_zip_f32", 2: "k_zipq_f32", 3: "k_zip64_f32", 4: "k_zip128_f32", 5: "k_zipm64_f32", 6: "k_zip_f64"}
+# ctn_walk_form (ctn_exec_walk_form): how a plan of small steps is walked in one launch
+WALK_FORMS = {0: None, 1: "k_chain", 2: "k_chain_lds"}
 GRAD_SCRATCH = 512          # doubles of scratch ctn_grad_seed needs (CTN_GRAD_SCRATCH)
 GRAD_MAX_DIMS = 64          # axes of an operand ctn_grad_leaf writes (CTN_GRAD_MAX_DIMS)
 CPLX_SCRATCH = 1024         # doubles of scratch ctn_cplx_normalize(_grad) needs (CTN_CPLX_SCRATCH)
@@ -163,6 +165,7 @@ def load_library():
         "ctn_exec_step_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "ctn_exec_step_tile": (i32, [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "ctn_exec_step_form": (i32, [vp, i32, C.POINTER(C.c_int32)]),
+        "ctn_exec_walk_form": (i32, [vp, C.POINTER(C.c_int32)]),
         "ctn_exec_set_rescale_mode": (i32, [vp, i32]),
         "ctn_exec_eager_reruns": (i32, [vp]),
         "ctn_exec_snapshot_scales": (i32, [vp, vp, i32, vp]),
@@ -565,6 +568,13 @@ class Executor:
             _check(self._lib.ctn_exec_step_form(self._h, self.plan.native_step(s), C.byref(form)))
             out.append(form.value)
         return out
+
+    def walk_form(self):
+        """How the plan is walked, decided when the executor was created: a key of `WALK_FORMS` (0: step by step, 1: one
+        launch of k_chain, 2: one launch of k_chain_lds - CTN_CHAIN=2; same bits as k_chain)."""
+        form = C.c_int32(0)
+        _check(self._lib.ctn_exec_walk_form(self._h, C.byref(form)))
+        return form.value
 
     def step_ms(self):
         ms = np.zeros(self.plan.n_steps, dtype=np.float32)

@@ -305,6 +305,21 @@ typedef enum {
 int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form);
 
 /*
+ * How the executor walks its plan (read-only; decided at ctn_exec_create, valid before the first enqueue).  A plan of
+ * 4 ... 4096 small steps is walked in ONE launch by a persistent workgroup per replica: by k_chain, or - CTN_CHAIN=2, and
+ * where the host-side packer accepts the plan - by k_chain_lds, which keeps step records, staged inputs and intermediates
+ * in LDS.  Both walkers perform the same operations in the same order: results, ctn_exec_step_rescales and the scale
+ * register are bit-identical.  CTN_WALK_NONE for every plan that runs step by step.  (Like ctn_exec_step_form, the entry
+ * point leaves CTN_ABI_VERSION as it is.)
+ */
+typedef enum {
+  CTN_WALK_NONE = 0,
+  CTN_WALK_CHAIN = 1,      /* k_chain */
+  CTN_WALK_CHAIN_LDS = 2   /* k_chain_lds */
+} ctn_walk_form;
+int ctn_exec_walk_form(const ctn_exec* exec, int32_t* form);
+
+/*
  * Per-step device timing with HIP events recorded on the executor's stream.
  * ctn_exec_set_timing(exec, slots): slots > 0 brackets every step's kernels of
  * the next `slots` enqueues with events (later enqueues run without events);
