@@ -18,7 +18,13 @@ recomputes the intermediates step by step and walks the path in reverse with one
 Everything runs on torch's current stream (or one side stream when torch is on the legacy default stream, whose
 handle the engine cannot take); the backward waits on the host at most once - for the per-step rescale flags, only
 when the root of a split-format result was not rescaled.  Double backward is not supported (``once_differentiable``).
+
+``CTN_GRAD_TAPE=1`` (read on every backward): the same pass as a backward tape (`BackwardSchedule.tape_records`,
+`engine.GradTape`; include/ctn_abi.h, ctn_grad_tape_*) - the walk's launches in the walk's order over an arena the tape
+owns, issued by one native call and replayed as one hipGraph from its third run on; the same bits.  The default is the
+walk.  `backward_stats()` counts the backwards by path.
 """
+import os
 import threading
 from collections import OrderedDict
 
@@ -99,6 +105,7 @@ class BackwardSchedule:
                 self.broadcast[child] = tuple(l for l in uniq if l not in self.cot_labels[child])
         self._plans = {}
         self._executors = {}
+        self._tapes = {}
         self._lock = threading.Lock()
 
     # -- structure ----------------------------------------------------------------------------------------------
@@ -199,9 +206,149 @@ class BackwardSchedule:
                 self._executors[key] = ex
         return ex
 
+    # -- the backward tape (CTN_GRAD_TAPE=1) ------------------------------------------------------------------------
+    def tape_records(self, need, frontier, grad_dtypes, has_gt=True, has_gc=True):
+        """The reverse pass of `_backward` as the record list of a backward tape (include/ctn_abi.h, ctn_grad_tape_*):
+        the same traversal, emitting a record where `_backward` launches.  Covers the data-independent case, every step
+        rescaled.  ``grad_dtypes``: numpy dtype of every operand's gradient.
+
+        Returns a dict: ``records`` and ``slots`` as `engine.GradTape` takes them, ``plans``, ``n_regs``, ``n_ext`` and
+        ``zero`` (operands whose gradient is exactly zero: no record writes it).  External slot ``j < n`` is operand
+        ``j``, ``n`` is ``g_t``, ``n + 1`` is ``g_c``, ``n + 2 + j`` the gradient of operand ``j``."""
+        n, S = self.n_inputs, self.n_steps
+        n_ids = n + S
+        es = self.dtype.itemsize
+        Z, LOG, G, SEED, ZERO = 0, n_ids, 2 * n_ids, 3 * n_ids, 4 * n_ids
+        records, slots, plans, plan_ix = [], [], [], {}
+
+        def arena(shape):
+            numel = 1
+            for d in shape:
+                numel *= int(d)
+            slots.append((0, -1, max(numel, 1) * es))
+            return len(slots) - 1
+
+        def external(idx, nbytes):
+            slots.append((1, idx, max(int(nbytes), es)))
+            return len(slots) - 1
+
+        def plan_index(plan):
+            if id(plan) not in plan_ix:
+                plan_ix[id(plan)] = len(plans)
+                plans.append(plan)
+            return plan_ix[id(plan)]
+
+        def numel_of(shape):
+            out = 1
+            for d in shape:
+                out *= int(d)
+            return out
+
+        def run(plan, a, b, out, log, dst, kids):
+            records.append({"kind": engine.TAPE_RUN, "plan": plan_index(plan), "in": [a] + ([b] if b is not None else []),
+                            "out": out, "reg": [log, dst] + list(kids), "src_dtype": self.dtype})
+
+        def leaf(src, g, dims, strides, first, dst_dtype, out):
+            records.append({"kind": engine.TAPE_LEAF, "in": [src], "out": out, "reg": [g if g is not None else -1],
+                            "src_dtype": self.dtype, "dst_dtype": dst_dtype, "dims": list(dims), "strides": list(strides),
+                            "first": list(first)})
+
+        # 1. recompute Z_hat_k and z_k
+        zhat = {i: external(i, numel_of(self.shapes[i]) * es) for i in range(n)}
+        last = S if self.split_format else S - 1
+        for k in range(last):
+            a, b, _out = self.steps[k]
+            plan = self.recompute_plan(k)
+            buf = arena(plan.out_shape)
+            run(plan, zhat[a], zhat[b] if b >= 0 else None, buf, LOG + n + k, Z + n + k, [Z + a] + ([Z + b] if b >= 0 else []))
+            zhat[n + k] = buf
+        frontier = set(frontier)
+        scratch = arena((engine.GRAD_SCRATCH * 8 // es,)) if frontier else None
+        g_t = external(n, numel_of(self.shape_of(self.labels[self.root])) * es) if has_gt else None
+        g_c = external(n + 1, es) if has_gc else None
+
+        # 2. the reverse walk
+        cot = {self.root: (g_t, self.labels[self.root], None)}
+
+        def expand(buf, labels, full):
+            if buf is None or tuple(labels) == tuple(full):
+                return buf
+            shp = self.shape_of(full)
+            dst = arena(shp)
+            leaf(buf, None, shp, _src_strides(full, labels, self), range(len(full)), self.dtype, dst)
+            return dst
+
+        for k, moves in self.walk(need, frontier):
+            i = n + k
+            buf, lab, g = cot.pop(i)
+            if k in frontier:
+                full = self.labels[i]
+                gh = expand(buf, lab, full)
+                out = arena(self.shape_of(full))
+                records.append({"kind": engine.TAPE_SEED, "in": [zhat[i], gh if gh is not None else -1,
+                                                                  g_c if g_c is not None else -1],
+                                "out": out, "aux": scratch, "reg": [Z + i, g if g is not None else -1, SEED + i],
+                                "src_dtype": self.dtype, "numel": numel_of(self.shape_of(full)), "min_norm": GRAD_MIN_NORM})
+                buf, g = out, SEED + i
+            for child, other, plan, out_l, below in moves:
+                if buf is None:
+                    cot[child] = (None, (), None)
+                    continue
+                if plan is None:
+                    cot[child] = (buf, out_l, g)
+                    continue
+                res = arena(plan.out_shape)
+                run(plan, buf, zhat[other], res, LOG + child, G + child,
+                    [g if g is not None else ZERO] + ([Z + other] if below else []))
+                cot[child] = (res, out_l, G + child)
+        # 3. the operands' gradients
+        zero = []
+        for j in range(n):
+            if not need[j]:
+                continue
+            buf, lab, g = cot.pop(j, (None, (), None))
+            if buf is None:
+                zero.append(j)
+                continue
+            shp = self.shapes[j]
+            labels = self.labels[j]
+            dt = np.dtype(grad_dtypes[j])
+            out = external(n + 2 + j, numel_of(shp) * dt.itemsize)
+            leaf(buf, g, shp, _src_strides(labels, lab, self), [labels.index(l) for l in labels], dt, out)
+        return {"records": records, "slots": slots, "plans": plans, "n_regs": 4 * n_ids + 1, "n_ext": 2 * n + 2,
+                "zero": zero}
+
+    def tape(self, need, grad_dtypes, has_gt, has_gc, device, stream):
+        """The cached backward tape of one (needs mask, gradient dtypes, which cotangents arrive, device, stream, thread)
+        as ``(engine.GradTape, its description)``, or None where there is none: no RUN record, an arena past the cap
+        (``CTN_GRAD_TAPE_MAX_BYTES``), or a device out of memory for the arena or the tape's executors - the caller walks
+        step by step then."""
+        key = (tuple(bool(x) for x in need[:self.n_inputs]), tuple(np.dtype(d).str for d in grad_dtypes), bool(has_gt),
+               bool(has_gc), device, stream, threading.get_ident())
+        with self._lock:
+            if key in self._tapes:
+                return self._tapes[key]
+        frontier = self.frontier([True] * self.n_steps)
+        d = self.tape_records(need, frontier, grad_dtypes, has_gt, has_gc)
+        hit = None
+        if any(r["kind"] == engine.TAPE_RUN for r in d["records"]):
+            try:
+                hit = (engine.GradTape(d["records"], d["slots"], d["n_ext"], d["n_regs"], d["plans"], device, stream), d)
+            except (engine.TapeRefused, MemoryError):
+                # the cap counts the arena only; a tape also holds one executor per RUN record (each with its own small
+                # device buffers), and a device that cannot hold those refuses with CTN_OOM.  The walk shares a few
+                # executors between all steps, so it may still fit.  Any other error is a fault, not a refusal: it rises.
+                hit = None
+        with self._lock:
+            self._tapes[key] = hit
+        return hit
+
     def close(self):
         with self._lock:
             exs, self._executors = list(self._executors.values()), {}
+            tapes, self._tapes = [t for t in self._tapes.values() if t is not None], {}
+        for tape, _d in tapes:
+            tape.close()
         for ex in exs:
             ex.close()
 
@@ -419,8 +566,82 @@ def _rejoin(torch, dev, side, results):
         t.record_stream(cur)
 
 
+_STATS_KEYS = ("walk", "tape_eager", "tape_captured", "tape_replayed")
+_STATS = dict.fromkeys(_STATS_KEYS, 0)
+_STATS_LOCK = threading.Lock()
+
+
+def backward_stats():
+    """How the backwards since the last `reset_backward_stats` ran: ``walk`` (step by step from Python), and with
+    ``CTN_GRAD_TAPE=1`` ``tape_eager`` / ``tape_captured`` / ``tape_replayed`` (a backward tape issued launch by launch,
+    under stream capture, as one graph launch)."""
+    with _STATS_LOCK:
+        return dict(_STATS)
+
+
+def reset_backward_stats():
+    with _STATS_LOCK:
+        for k in _STATS_KEYS:
+            _STATS[k] = 0
+
+
+def _count(key):
+    with _STATS_LOCK:
+        _STATS[key] += 1
+
+
+def _backward_tape(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c):
+    """`_backward` through a backward tape: one native call.  None where the schedule has no tape (the caller walks)."""
+    dev = ops[0].device
+    tdt = ops[0].dtype
+    n = sch.n_inputs
+    need = sch.needs(needs_input_grad)
+    stream, side = _stream_for(torch, dev)
+    devi = dev.index or 0
+    np_of = {torch.float32: np.float32, torch.float64: np.float64}
+    with torch.cuda.stream(side) if side is not None else _NullCtx():
+        hit = sch.tape(need, [np_of.get(d, np.float64) for d in in_dtypes], g_t is not None, g_c is not None, devi, stream)
+        if hit is None:
+            return None
+        tape, desc = hit
+        if side is not None:
+            for t in list(ops) + [x for x in (g_t, g_c) if x is not None]:
+                t.record_stream(side)
+
+        def dense(x):
+            if x is None:
+                return None
+            x = x.to(device=dev, dtype=tdt).contiguous()
+            return x.clone() if x.data_ptr() % 16 else x
+
+        g_t, g_c = dense(g_t), dense(g_c)
+        # fresh on every call: torch may keep a gradient as .grad, the tape writes its arena again
+        grads = [None] * n
+        for j in range(n):
+            if need[j]:
+                make = torch.zeros if j in desc["zero"] else torch.empty
+                grads[j] = make(tuple(ops[j].shape), dtype=in_dtypes[j], device=dev)
+        ext = [o.data_ptr() for o in ops] + [g_t.data_ptr() if g_t is not None else 0,
+                                             g_c.data_ptr() if g_c is not None else 0]
+        ext += [g.data_ptr() if g is not None else 0 for g in grads]
+        before = tape.info()
+        tape.run(ext)
+        after = tape.info()
+        for key in ("eager", "captured", "replayed"):
+            if after[key] > before[key]:
+                _count("tape_" + key)
+    _rejoin(torch, dev, side, [t for t in grads if t is not None])
+    return grads
+
+
 def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_rescaled):
     """Gradients of every operand (None where not needed) - see the module docstring."""
+    if os.environ.get("CTN_GRAD_TAPE", "0") == "1" and (root_rescaled or not sch.split_format):
+        # the data-independent case as one native call (a split-format root that was not rescaled needs the host wait)
+        grads = _backward_tape(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c)
+        if grads is not None:
+            return grads
+    _count("walk")
     dev = ops[0].device
     tdt = ops[0].dtype
     n, S = sch.n_inputs, sch.n_steps

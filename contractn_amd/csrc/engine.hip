@@ -17,6 +17,7 @@
 // Written for CDNA4 only: 64-lane waves, v_mfma_f32_32x32x2_f32, 160 KiB LDS/CU.
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -27,6 +28,7 @@
 #include "plan.h"
 #include "chain_pack.h"
 #include "cplx_match.h"
+#include "grad_tape.h"
 
 #include "kernel_args.h"
 #include "kernels_mfma.h"
@@ -2819,6 +2821,309 @@ int ctn_grad_leaf(ctn_exec* exec, int src_dtype, const void* src, const double* 
   HIPCHECK(hipGetLastError());
   return CTN_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Backward tape (include/ctn_abi.h, ctn_grad_tape_*; grad_tape.h holds the host logic).  A reverse pass as a fixed
+// sequence over fixed buffers: one executor per RUN record (an executor has ONE pointer table, and a replayed graph reads
+// whatever that table holds at replay time), SEED and LEAF through the tape's own table of slot addresses.  Everything
+// that depends on the caller's tensors - that table and the pointer tables of the RUN records with an external slot - is
+// uploaded in front of the sequence, never inside it.
+// ---------------------------------------------------------------------------
+struct ctn_grad_tape {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::vector<ctn_tape_record> recs;
+  std::vector<ctn_tape_slot> slots;
+  std::vector<const ctn_plan*> plans;
+  std::vector<int64_t> off;
+  std::vector<int> slot_align;           // per slot: the largest element size a record reads or writes there
+  std::vector<GradLeafArgs> leaf;        // per record (LEAF only)
+  std::vector<ctn_exec*> execs;          // per record (RUN only)
+  std::vector<int> ext_runs;             // RUN records with an external slot: pointer table refreshed on every run
+  int n_ext = 0, n_regs = 0, n_execs = 0;
+  int64_t arena_bytes = 0, regs_bytes = 0;
+  char* d_arena = nullptr;
+  void** d_tab = nullptr;                // [n_slots] slot addresses
+  std::vector<void*> h_tab;
+  bool tab_valid = false;
+  int use_graph = 1;
+  bool warm = false;
+  hipGraphExec_t graph_exec = nullptr;
+  int64_t n_eager = 0, n_captured = 0, n_replayed = 0;
+  int64_t device_bytes = 0, create_us = 0;   // what creation took from the device (arena, table, executors) and how long
+
+  ~ctn_grad_tape() {
+    DeviceGuard dg(device);
+    // hipFree waits for the device: nothing of the last run is in flight when the graph and the executors go (the
+    // stream is the caller's and may be gone by now: it is not touched here)
+    if (d_arena) (void)hipFree(d_arena);
+    if (d_tab) (void)hipFree(d_tab);
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    for (ctn_exec* x : execs)
+      if (x) ctn_exec_destroy(x);
+  }
+  double* reg(int i) const { return i < 0 ? nullptr : (double*)d_arena + i; }
+};
+
+static int64_t tape_slot_bytes(const ctn_grad_tape* T, int s) { return T->slots[s].external ? INT64_MAX : T->slots[s].bytes; }
+
+// Sizes: every arena slot a record touches is large enough for what the kernels read and write there.
+static const char* tape_check_sizes(const ctn_grad_tape* T, const ctn_tape_desc& d) {
+  for (size_t i = 0; i < T->recs.size(); ++i) {
+    const ctn_tape_record& r = T->recs[i];
+    if (r.kind == CTN_TAPE_RUN) {
+      const Plan& P = T->plans[r.plan]->p;
+      if (P.n_steps != 1 || P.n_inputs != (r.in[1] >= 0 ? 2 : 1) || r.src_dtype != P.dtype) return "a RUN record needs a one-step plan of its arity and dtype";
+      const int64_t es = P.elem_size();
+      for (int j = 0; j < P.n_inputs; ++j)
+        if (P.tensors[j].numel * es > tape_slot_bytes(T, r.in[j])) return "a RUN record's operand is larger than its slot";
+      if (ctn_plan_out_bytes(T->plans[r.plan]) > tape_slot_bytes(T, r.out)) return "a RUN record's result is larger than its slot";
+    } else if (r.kind == CTN_TAPE_SEED) {
+      const int64_t b = r.numel * (r.src_dtype == CTN_F64 ? 8 : 4);
+      if (b > tape_slot_bytes(T, r.in[0]) || (r.in[1] >= 0 && b > tape_slot_bytes(T, r.in[1])) || b > tape_slot_bytes(T, r.out))
+        return "a SEED record's tensors are larger than their slots";
+    } else {
+      int64_t numel = 1, reach = 0;
+      for (int a = 0; a < r.ndim; ++a) {
+        const int64_t dim = d.leaf_dims[r.axes + a], st = d.leaf_strides[r.axes + a];
+        const int32_t f = d.leaf_first[r.axes + a];
+        if (dim < 0 || st < 0 || f < 0 || f > a || (f != a && d.leaf_dims[r.axes + f] != dim)) return "a LEAF record's axis description is inconsistent";
+        numel *= dim;
+        if (f == a && dim > 0) reach += (dim - 1) * st;
+      }
+      if (numel > 0 && (reach + 1) * (r.src_dtype == CTN_F64 ? 8 : 4) > tape_slot_bytes(T, r.in[0])) return "a LEAF record reads past its source slot";
+      if (numel * (r.dst_dtype == CTN_F64 ? 8 : 4) > tape_slot_bytes(T, r.out)) return "a LEAF record writes past its destination slot";
+    }
+  }
+  return nullptr;
+}
+
+static int tape_set_run_pointers(ctn_grad_tape* T, int i) {
+  const ctn_tape_record& r = T->recs[i];
+  const void* ins[2] = {T->h_tab[r.in[0]], r.in[1] >= 0 ? T->h_tab[r.in[1]] : nullptr};
+  void* outs[1] = {T->h_tab[r.out]};
+  return exec_set_pointers(&T->execs[i]->e, ins, outs);
+}
+
+// The whole sequence on the tape's stream: nothing here depends on the caller's pointers, nothing copies from the host.
+static int tape_issue(ctn_grad_tape* T) {
+  hipStream_t st = T->stream;
+  double* regs = (double*)T->d_arena;
+  HIPCHECK(hipMemsetAsync(regs, 0, (size_t)T->regs_bytes, st));
+  for (size_t i = 0; i < T->recs.size(); ++i) {
+    const ctn_tape_record& r = T->recs[i];
+    if (r.kind == CTN_TAPE_RUN) {
+      Exec* E = &T->execs[i]->e;
+      exec_new_run(E);
+      const int rc = exec_launch_all(E);
+      if (rc != CTN_OK) return rc;
+      hipLaunchKernelGGL(k_tape_regs, dim3(1), dim3(64), 0, st, (const double*)E->d_log, regs, r.reg[0], r.reg[1], r.reg[2], r.reg[3]);
+    } else if (r.kind == CTN_TAPE_SEED) {
+      const int64_t numel = r.numel;
+      const int nb = (int)std::min<int64_t>((numel + 255) / 256, kGradSeedBlocks);
+      const int dot_parts = r.in[1] >= 0 ? nb : 0;
+      double* scratch = (double*)(T->d_arena + T->off[r.aux]);
+      void* const* tab = T->d_tab;
+      if (r.src_dtype == CTN_F32) {
+        if (r.in[1] >= 0) hipLaunchKernelGGL(k_grad_seed_dot_tab<float>, dim3(nb), dim3(256), 0, st, tab, r.in[1], r.in[0], numel, scratch);
+        hipLaunchKernelGGL(k_grad_seed_apply_tab<float>, dim3(nb), dim3(256), 0, st, tab, r.in[1], r.in[0], numel, r.in[2],
+                           (const double*)T->reg(r.reg[1]), dot_parts, scratch, r.out);
+        hipLaunchKernelGGL(k_grad_seed_norm_tab<float>, dim3(nb), dim3(256), 0, st, tab, r.out, numel, (const double*)T->reg(r.reg[0]),
+                           (const double*)T->reg(r.reg[1]), nb, (const double*)scratch, r.min_norm, T->reg(r.reg[2]));
+      } else {
+        if (r.in[1] >= 0) hipLaunchKernelGGL(k_grad_seed_dot_tab<double>, dim3(nb), dim3(256), 0, st, tab, r.in[1], r.in[0], numel, scratch);
+        hipLaunchKernelGGL(k_grad_seed_apply_tab<double>, dim3(nb), dim3(256), 0, st, tab, r.in[1], r.in[0], numel, r.in[2],
+                           (const double*)T->reg(r.reg[1]), dot_parts, scratch, r.out);
+        hipLaunchKernelGGL(k_grad_seed_norm_tab<double>, dim3(nb), dim3(256), 0, st, tab, r.out, numel, (const double*)T->reg(r.reg[0]),
+                           (const double*)T->reg(r.reg[1]), nb, (const double*)scratch, r.min_norm, T->reg(r.reg[2]));
+      }
+    } else {
+      const GradLeafArgs& a = T->leaf[i];
+      if (a.numel == 0) continue;
+      const dim3 grid((unsigned)std::min<int64_t>((a.numel + 255) / 256, 4096));
+      const double* g = T->reg(r.reg[0]);
+      void* const* tab = T->d_tab;
+      if (r.src_dtype == CTN_F32 && r.dst_dtype == CTN_F32)
+        hipLaunchKernelGGL((k_grad_leaf_tab<float, float>), grid, dim3(256), 0, st, a, tab, r.in[0], g, r.out);
+      else if (r.src_dtype == CTN_F32)
+        hipLaunchKernelGGL((k_grad_leaf_tab<float, double>), grid, dim3(256), 0, st, a, tab, r.in[0], g, r.out);
+      else if (r.dst_dtype == CTN_F32)
+        hipLaunchKernelGGL((k_grad_leaf_tab<double, float>), grid, dim3(256), 0, st, a, tab, r.in[0], g, r.out);
+      else
+        hipLaunchKernelGGL((k_grad_leaf_tab<double, double>), grid, dim3(256), 0, st, a, tab, r.in[0], g, r.out);
+    }
+  }
+  HIPCHECK(hipGetLastError());
+  return CTN_OK;
+}
+
+int ctn_grad_tape_create(const ctn_tape_desc* desc, int device, void* stream, ctn_grad_tape** out) {
+  if (!desc || !out || !stream) { g_err = "invalid argument to ctn_grad_tape_create"; return CTN_INVALID_ARG; }
+  *out = nullptr;
+  std::vector<TapeLife> life;
+  std::string why = tape_check_records(*desc, &life);
+  if (!why.empty()) { g_err = "ctn_grad_tape_create: " + why; return CTN_INVALID_ARG; }
+  for (int p = 0; p < desc->n_plans; ++p)
+    if (!desc->plans || !desc->plans[p]) { g_err = "ctn_grad_tape_create: NULL plan"; return CTN_INVALID_ARG; }
+  ctn_grad_tape* T = new (std::nothrow) ctn_grad_tape();
+  if (!T) { g_err = "out of host memory"; return CTN_OOM; }
+  // a failed creation leaves no HIP error behind: the caller may walk step by step instead (CTN_UNSUPPORTED, CTN_OOM)
+  auto fail = [&](int code) { delete T; (void)hipGetLastError(); return code; };
+  const auto t_begin = std::chrono::steady_clock::now();
+  T->device = device;
+  T->recs.assign(desc->records, desc->records + desc->n_records);
+  T->slots.assign(desc->slots, desc->slots + desc->n_slots);
+  if (desc->n_plans) T->plans.assign(desc->plans, desc->plans + desc->n_plans);
+  T->n_ext = desc->n_ext; T->n_regs = desc->n_regs;
+  T->regs_bytes = tape_round_up((int64_t)desc->n_regs * 8);
+  T->arena_bytes = tape_layout(*desc, life, &T->off);
+  why = tape_check_layout(*desc, life, T->off, T->arena_bytes);
+  if (!why.empty()) { g_err = "ctn_grad_tape_create: " + why; return fail(CTN_INVALID_ARG); }
+  if (const char* bad = tape_check_sizes(T, *desc)) { g_err = std::string("ctn_grad_tape_create: ") + bad; return fail(CTN_INVALID_ARG); }
+  const int64_t cap = desc->max_bytes > 0 ? desc->max_bytes : kTapeDefaultMaxBytes;
+  if (T->arena_bytes > cap) {
+    g_err = "ctn_grad_tape_create: the arena needs " + std::to_string(T->arena_bytes) + " bytes, more than the cap of " + std::to_string(cap);
+    return fail(CTN_UNSUPPORTED);
+  }
+  T->leaf.resize(T->recs.size());
+  T->slot_align.assign(desc->n_slots, 4);
+  for (size_t i = 0; i < T->recs.size(); ++i) {
+    const ctn_tape_record& r = T->recs[i];
+    const int es_in = r.src_dtype == CTN_F64 ? 8 : 4, es_out = r.kind == CTN_TAPE_LEAF ? (r.dst_dtype == CTN_F64 ? 8 : 4) : es_in;
+    for (int j = 0; j < 3; ++j)
+      if (r.in[j] >= 0) T->slot_align[r.in[j]] = std::max(T->slot_align[r.in[j]], es_in);
+    T->slot_align[r.out] = std::max(T->slot_align[r.out], es_out);
+    if (r.kind != CTN_TAPE_LEAF) continue;
+    GradLeafArgs a{};
+    a.ndim = r.ndim;
+    int64_t numel = 1;
+    for (int d = r.ndim - 1; d >= 0; --d) {
+      const int32_t f = desc->leaf_first[r.axes + d];
+      a.dims[d] = desc->leaf_dims[r.axes + d];
+      a.dst_stride[d] = numel;
+      a.src_stride[d] = f == d ? desc->leaf_strides[r.axes + d] : 0;
+      a.first[d] = f;
+      numel *= a.dims[d];
+    }
+    a.numel = numel;
+    T->leaf[i] = a;
+  }
+  int ndev = 0;
+  int rc = ctn_device_count(&ndev);
+  if (rc != CTN_OK) return fail(rc);
+  if (device < 0 || device >= ndev) { g_err = "device index out of range"; return fail(CTN_INVALID_ARG); }
+  DeviceGuard dg(device);
+  if (dg.err != hipSuccess) { g_err = "hipSetDevice failed"; return fail(CTN_HIP_ERROR); }
+  T->stream = (hipStream_t)stream;
+  T->use_graph = read_dev_switches().graph;
+#define HIPCHECK_T(expr)                                                        \
+  do {                                                                          \
+    hipError_t e_ = (expr);                                                     \
+    if (e_ != hipSuccess) {                                                     \
+      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
+      return fail(e_ == hipErrorOutOfMemory ? CTN_OOM : CTN_HIP_ERROR);         \
+    }                                                                           \
+  } while (0)
+  size_t free_before = 0, free_after = 0, total_mem = 0;
+  HIPCHECK_T(hipMemGetInfo(&free_before, &total_mem));
+  HIPCHECK_T(hipMalloc((void**)&T->d_arena, (size_t)T->arena_bytes));
+  HIPCHECK_T(hipMalloc((void**)&T->d_tab, (size_t)desc->n_slots * sizeof(void*)));
+  T->h_tab.assign(desc->n_slots, nullptr);
+  for (int s = 0; s < desc->n_slots; ++s)
+    if (!T->slots[s].external && T->off[s] >= 0) T->h_tab[s] = T->d_arena + T->off[s];
+  T->execs.assign(T->recs.size(), nullptr);
+  for (size_t i = 0; i < T->recs.size(); ++i) {
+    const ctn_tape_record& r = T->recs[i];
+    if (r.kind != CTN_TAPE_RUN) continue;
+    rc = ctn_exec_create(T->plans[r.plan], device, stream, 1, &T->execs[i]);
+    if (rc != CTN_OK) return fail(rc);
+    ++T->n_execs;
+    (void)ctn_exec_set_rescale_mode(T->execs[i], 1);       // eager: one-step runs are never "suspect", nothing to fetch
+    const bool ext = T->slots[r.in[0]].external || (r.in[1] >= 0 && T->slots[r.in[1]].external);
+    if (ext) { T->ext_runs.push_back((int)i); continue; }
+    rc = tape_set_run_pointers(T, (int)i);                  // all in the arena: set once, before any capture
+    if (rc != CTN_OK) return fail(rc);
+  }
+  HIPCHECK_T(hipMemGetInfo(&free_after, &total_mem));
+#undef HIPCHECK_T
+  T->device_bytes = free_before > free_after ? (int64_t)(free_before - free_after) : 0;
+  T->create_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_begin).count();
+  *out = T;
+  return CTN_OK;
+}
+
+int ctn_grad_tape_run(ctn_grad_tape* T, void* const* ext, int n_ext) {
+  if (!T || n_ext != T->n_ext || (n_ext > 0 && !ext)) { g_err = "invalid argument to ctn_grad_tape_run"; return CTN_INVALID_ARG; }
+  DeviceGuard dg(T->device);
+  HIPCHECK(dg.err);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool foreign_capture = hipStreamIsCapturing(T->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  if (foreign_capture) (void)hipGetLastError();
+  // 1. everything that follows the caller's tensors, in front of the sequence
+  // every pointer is checked before h_tab is touched: a refused call leaves the tape as it was
+  for (size_t s = 0; s < T->slots.size(); ++s) {
+    if (!T->slots[s].external) continue;
+    void* p = ext[T->slots[s].ext_index];
+    if (!p) { g_err = "ctn_grad_tape_run: NULL external pointer"; return CTN_INVALID_ARG; }
+    if ((uintptr_t)p % T->slot_align[s]) { g_err = "ctn_grad_tape_run: external pointers must be element aligned"; return CTN_INVALID_ARG; }
+  }
+  bool changed = !T->tab_valid;
+  for (size_t s = 0; s < T->slots.size(); ++s) {
+    if (!T->slots[s].external) continue;
+    void* p = ext[T->slots[s].ext_index];
+    if (T->h_tab[s] != p) { T->h_tab[s] = p; changed = true; }
+  }
+  if (changed) {
+    T->tab_valid = false;                    // until the upload is queued: a failure below uploads again next time
+    HIPCHECK(hipMemcpyAsync(T->d_tab, T->h_tab.data(), T->h_tab.size() * sizeof(void*), hipMemcpyHostToDevice, T->stream));
+    T->tab_valid = true;
+  }
+  for (int i : T->ext_runs) {
+    const int rc = tape_set_run_pointers(T, i);
+    if (rc != CTN_OK) return rc;
+  }
+  // 2. the sequence: eager, captured, replayed (as exec_launch_all)
+  if (!T->use_graph || foreign_capture) { ++T->n_eager; return tape_issue(T); }
+  if (!T->graph_exec) {
+    if (!T->warm) { T->warm = true; ++T->n_eager; return tape_issue(T); }
+    hipGraph_t g = nullptr;
+    if (hipStreamBeginCapture(T->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+      (void)hipGetLastError();
+      T->use_graph = 0;
+      ++T->n_eager;
+      return tape_issue(T);
+    }
+    const int rc = tape_issue(T);
+    const hipError_t ec = hipStreamEndCapture(T->stream, &g);
+    if (rc != CTN_OK || ec != hipSuccess || !g || hipGraphInstantiate(&T->graph_exec, g, nullptr, nullptr, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      if (g) (void)hipGraphDestroy(g);
+      T->graph_exec = nullptr;
+      T->use_graph = 0;                      // eager for good
+      if (rc != CTN_OK) return rc;
+      ++T->n_eager;
+      return tape_issue(T);
+    }
+    (void)hipGraphDestroy(g);
+    HIPCHECK(hipGraphLaunch(T->graph_exec, T->stream));
+    ++T->n_captured;
+    return CTN_OK;
+  }
+  HIPCHECK(hipGraphLaunch(T->graph_exec, T->stream));
+  ++T->n_replayed;
+  return CTN_OK;
+}
+
+int ctn_grad_tape_info(const ctn_grad_tape* T, int64_t* info) {
+  if (!T || !info) { g_err = "invalid argument to ctn_grad_tape_info"; return CTN_INVALID_ARG; }
+  info[0] = (int64_t)T->recs.size(); info[1] = T->arena_bytes; info[2] = T->n_execs;
+  info[3] = T->n_eager; info[4] = T->n_captured; info[5] = T->n_replayed;
+  info[6] = T->regs_bytes; info[7] = (int64_t)T->slots.size();
+  info[8] = T->device_bytes; info[9] = T->create_us;
+  return CTN_OK;
+}
+
+void ctn_grad_tape_destroy(ctn_grad_tape* tape) { delete tape; }
 
 static_assert(kCplxBlocks <= CTN_CPLX_SCRATCH, "one scratch double per workgroup of the complex reductions");
 static bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }

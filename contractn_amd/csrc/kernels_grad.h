@@ -18,9 +18,10 @@ namespace ctn {
 // ---------------------------------------------------------------------------
 constexpr int kGradSeedBlocks = 256;
 
+// The bodies are shared with the *_tab entry kernels of the backward tape below: one text, the same bits.
 template <typename T>
-__global__ __launch_bounds__(256) void k_grad_seed_dot(const T* __restrict__ g_hat, const T* __restrict__ t_hat,
-                                                       int64_t n, double* __restrict__ scratch) {
+__device__ __forceinline__ void grad_seed_dot_body(const T* __restrict__ g_hat, const T* __restrict__ t_hat, int64_t n,
+                                                   double* __restrict__ scratch) {
   __shared__ double red[4];
   double v = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
@@ -30,10 +31,9 @@ __global__ __launch_bounds__(256) void k_grad_seed_dot(const T* __restrict__ g_h
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void k_grad_seed_apply(const T* __restrict__ g_hat, const T* __restrict__ t_hat,
-                                                         int64_t n, const T* __restrict__ g_c,
-                                                         const double* __restrict__ g_in, int dot_parts,
-                                                         double* __restrict__ scratch, T* __restrict__ out) {
+__device__ __forceinline__ void grad_seed_apply_body(const T* __restrict__ g_hat, const T* __restrict__ t_hat, int64_t n,
+                                                     const T* __restrict__ g_c, const double* __restrict__ g_in,
+                                                     int dot_parts, double* __restrict__ scratch, T* __restrict__ out) {
   __shared__ double red[4];
   double dot = 0.0;
   for (int j = 0; j < dot_parts; ++j) dot += scratch[j];          // same order in every thread of every workgroup
@@ -53,10 +53,10 @@ __global__ __launch_bounds__(256) void k_grad_seed_apply(const T* __restrict__ g
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void k_grad_seed_norm(T* __restrict__ out, int64_t n, const double* __restrict__ z,
-                                                        const double* __restrict__ g_in, int parts,
-                                                        const double* __restrict__ scratch, double min_norm,
-                                                        double* __restrict__ g_out) {
+__device__ __forceinline__ void grad_seed_norm_body(T* __restrict__ out, int64_t n, const double* __restrict__ z,
+                                                    const double* __restrict__ g_in, int parts,
+                                                    const double* __restrict__ scratch, double min_norm,
+                                                    double* __restrict__ g_out) {
   double norm = 0.0;
   for (int j = 0; j < parts; ++j) norm += scratch[kGradSeedBlocks + j];
   const bool resc = norm > min_norm;
@@ -66,6 +66,28 @@ __global__ __launch_bounds__(256) void k_grad_seed_norm(T* __restrict__ out, int
       out[i] = (T)((double)out[i] / mean);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     g_out[0] = (g_in ? g_in[0] : 0.0) - z[0] + (resc ? log(mean) : 0.0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_dot(const T* __restrict__ g_hat, const T* __restrict__ t_hat,
+                                                       int64_t n, double* __restrict__ scratch) {
+  grad_seed_dot_body<T>(g_hat, t_hat, n, scratch);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_apply(const T* __restrict__ g_hat, const T* __restrict__ t_hat,
+                                                         int64_t n, const T* __restrict__ g_c,
+                                                         const double* __restrict__ g_in, int dot_parts,
+                                                         double* __restrict__ scratch, T* __restrict__ out) {
+  grad_seed_apply_body<T>(g_hat, t_hat, n, g_c, g_in, dot_parts, scratch, out);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_norm(T* __restrict__ out, int64_t n, const double* __restrict__ z,
+                                                        const double* __restrict__ g_in, int parts,
+                                                        const double* __restrict__ scratch, double min_norm,
+                                                        double* __restrict__ g_out) {
+  grad_seed_norm_body<T>(out, n, z, g_in, parts, scratch, min_norm, g_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -87,8 +109,8 @@ struct GradLeafArgs {
 };
 
 template <typename TS, typename TD>
-__global__ __launch_bounds__(256) void k_grad_leaf(GradLeafArgs a, const TS* __restrict__ src,
-                                                   const double* __restrict__ g, TD* __restrict__ dst) {
+__device__ __forceinline__ void grad_leaf_body(const GradLeafArgs& a, const TS* __restrict__ src,
+                                               const double* __restrict__ g, TD* __restrict__ dst) {
   const double m = g ? exp(g[0]) : 1.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.numel; i += (int64_t)gridDim.x * 256) {
     int64_t off = 0;
@@ -105,6 +127,63 @@ __global__ __launch_bounds__(256) void k_grad_leaf(GradLeafArgs a, const TS* __r
     const double v = on ? (double)src[off] : 0.0;
     dst[i] = (TD)(v == 0.0 ? 0.0 : v * m);
   }
+}
+
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void k_grad_leaf(GradLeafArgs a, const TS* __restrict__ src,
+                                                   const double* __restrict__ g, TD* __restrict__ dst) {
+  grad_leaf_body<TS, TD>(a, src, g, dst);
+}
+
+// ---------------------------------------------------------------------------
+// The backward tape (include/ctn_abi.h, ctn_grad_tape_*): the same kernels with every tensor pointer read from the
+// tape's device table of slot addresses, tab[slot] (slot < 0: nullptr), so that a captured launch follows the caller's
+// tensors from run to run.  They call the bodies of the kernels above with the same launch geometry: same bits.
+// ---------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T* tape_ptr(void* const* __restrict__ tab, int slot) {
+  return slot < 0 ? nullptr : (T*)tab[slot];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_dot_tab(void* const* __restrict__ tab, int s_g, int s_t, int64_t n,
+                                                           double* __restrict__ scratch) {
+  grad_seed_dot_body<T>(tape_ptr<const T>(tab, s_g), tape_ptr<const T>(tab, s_t), n, scratch);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_apply_tab(void* const* __restrict__ tab, int s_g, int s_t, int64_t n,
+                                                             int s_gc, const double* __restrict__ g_in, int dot_parts,
+                                                             double* __restrict__ scratch, int s_out) {
+  grad_seed_apply_body<T>(tape_ptr<const T>(tab, s_g), tape_ptr<const T>(tab, s_t), n, tape_ptr<const T>(tab, s_gc), g_in,
+                          dot_parts, scratch, tape_ptr<T>(tab, s_out));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_grad_seed_norm_tab(void* const* __restrict__ tab, int s_out, int64_t n,
+                                                            const double* __restrict__ z, const double* __restrict__ g_in,
+                                                            int parts, const double* __restrict__ scratch, double min_norm,
+                                                            double* __restrict__ g_out) {
+  grad_seed_norm_body<T>(tape_ptr<T>(tab, s_out), n, z, g_in, parts, scratch, min_norm, g_out);
+}
+
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void k_grad_leaf_tab(GradLeafArgs a, void* const* __restrict__ tab, int s_src,
+                                                       const double* __restrict__ g, int s_dst) {
+  grad_leaf_body<TS, TD>(a, tape_ptr<const TS>(tab, s_src), g, tape_ptr<TD>(tab, s_dst));
+}
+
+// k_tape_regs: the register work behind a RUN record in one launch - regs[r_log] = the run's log register (what
+// ctn_exec_snapshot_scales copies) and regs[r_dst] = regs[r_log] + regs[k0] + regs[k1], added left to right as
+// k_scales_add adds them (k < 0: no such term).  One lane, plain vector stores.
+__global__ __launch_bounds__(64) void k_tape_regs(const double* __restrict__ run_log, double* __restrict__ regs, int r_log,
+                                                  int r_dst, int k0, int k1) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double v = run_log[0];
+  regs[r_log] = v;
+  if (k0 >= 0) v += regs[k0];
+  if (k1 >= 0) v += regs[k1];
+  regs[r_dst] = v;
 }
 
 }  // namespace ctn

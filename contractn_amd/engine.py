@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "ctn_exec_set_finish_mode", "ctn_exec_finish",
     "ctn_grad_seed", "ctn_grad_leaf",
     "ctn_cplx_normalize", "ctn_cplx_normalize_grad",
+    "ctn_grad_tape_create", "ctn_grad_tape_run", "ctn_grad_tape_info", "ctn_grad_tape_destroy",
 )
 # ctn_step_form (ctn_exec_step_form): the fused zipper-pair kernel a step ran as
 STEP_FORMS = {0: None, 1: "k_zip_f32", 2: "k_zipq_f32", 3: "k_zip64_f32", 4: "k_zip128_f32", 5: "k_zipm64_f32", 6: "k_zip_f64"}
@@ -51,6 +52,10 @@ WALK_FORMS = {0: None, 1: "k_chain", 2: "k_chain_lds"}
 GRAD_SCRATCH = 512          # doubles of scratch ctn_grad_seed needs (CTN_GRAD_SCRATCH)
 GRAD_MAX_DIMS = 64          # axes of an operand ctn_grad_leaf writes (CTN_GRAD_MAX_DIMS)
 CPLX_SCRATCH = 1024         # doubles of scratch ctn_cplx_normalize(_grad) needs (CTN_CPLX_SCRATCH)
+TAPE_RUN, TAPE_SEED, TAPE_LEAF = 0, 1, 2     # ctn_tape_kind
+TAPE_MAX_BYTES = 1 << 30    # default cap of a backward tape's arena (CTN_GRAD_TAPE_MAX_BYTES overrides)
+TAPE_INFO = ("records", "arena_bytes", "executors", "eager", "captured", "replayed", "regs_bytes", "slots",
+             "device_bytes", "create_us")
 
 
 class PlanDesc(C.Structure):
@@ -89,6 +94,28 @@ class StepInfo(C.Structure):
         ("tile_n", C.c_int32),
         ("epilogue_sum", C.c_int32),
         ("reserved", C.c_int32),
+    ]
+
+
+class TapeRecord(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("plan", C.c_int32), ("in_", C.c_int32 * 3), ("out", C.c_int32), ("aux", C.c_int32),
+        ("reg", C.c_int32 * 4), ("src_dtype", C.c_int32), ("dst_dtype", C.c_int32), ("ndim", C.c_int32),
+        ("axes", C.c_int32), ("reserved", C.c_int32), ("numel", C.c_int64), ("min_norm", C.c_double),
+    ]
+
+
+class TapeSlot(C.Structure):
+    _fields_ = [("external", C.c_int32), ("ext_index", C.c_int32), ("bytes", C.c_int64)]
+
+
+class TapeDesc(C.Structure):
+    _fields_ = [
+        ("n_records", C.c_int32), ("n_slots", C.c_int32), ("n_ext", C.c_int32), ("n_regs", C.c_int32),
+        ("n_plans", C.c_int32), ("n_axes", C.c_int32),
+        ("records", C.POINTER(TapeRecord)), ("slots", C.POINTER(TapeSlot)), ("plans", C.POINTER(C.c_void_p)),
+        ("leaf_dims", C.POINTER(C.c_int64)), ("leaf_strides", C.POINTER(C.c_int64)), ("leaf_first", C.POINTER(C.c_int32)),
+        ("max_bytes", C.c_int64),
     ]
 
 
@@ -181,6 +208,10 @@ def load_library():
                                 C.POINTER(C.c_int32), i32, vp]),
         "ctn_cplx_normalize": (i32, [vp, i32, vp, vp, i32, i64, vp, vp, vp, vp]),
         "ctn_cplx_normalize_grad": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp]),
+        "ctn_grad_tape_create": (i32, [C.POINTER(TapeDesc), i32, vp, C.POINTER(vp)]),
+        "ctn_grad_tape_run": (i32, [vp, C.POINTER(vp), i32]),
+        "ctn_grad_tape_info": (i32, [vp, C.POINTER(C.c_int64)]),
+        "ctn_grad_tape_destroy": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -596,3 +627,94 @@ class Executor:
 
     def __del__(self):
         self.close()
+
+
+class TapeRefused(Exception):
+    """The arena of a backward tape would exceed its cap: the caller walks step by step instead."""
+
+
+class GradTape:
+    """A whole reverse pass as one native object (include/ctn_abi.h, ctn_grad_tape_*): ``run(ext_ptrs)`` issues it, from
+    the third run on as one graph launch.
+
+    ``records``: dicts with the fields of ``ctn_tape_record`` (``kind``, ``plan`` - an index into ``plans`` -, ``in`` (up to
+    three slots), ``out``, ``aux``, ``reg`` (up to four registers), ``src_dtype`` / ``dst_dtype`` as numpy dtypes, and for
+    a LEAF ``dims`` / ``strides`` / ``first``, for a SEED ``numel`` / ``min_norm``); ``slots``: ``(external, ext_index,
+    bytes)``.  One thread at a time, like an `Executor`."""
+
+    def __init__(self, records, slots, n_ext, n_regs, plans, device, stream, max_bytes=None):
+        lib = load_library()
+        if device_count() == 0:
+            raise RuntimeError(f"no HIP device visible: the contraction engine has no CPU fallback "
+                               f"({lib.ctn_last_error().decode()})")
+        self._lib = lib
+        self._h = None
+        self.plans = list(plans)          # borrowed by the native tape: kept alive here
+        self.n_ext = int(n_ext)
+        desc, keep = tape_desc(records, slots, n_ext, n_regs, self.plans, max_bytes)
+        handle = C.c_void_p()
+        rc = lib.ctn_grad_tape_create(C.byref(desc), int(device), C.c_void_p(stream), C.byref(handle))
+        del keep
+        if rc == -3:
+            raise TapeRefused(lib.ctn_last_error().decode("utf-8", "replace"))
+        _check(rc)
+        self._h = handle
+        self._ext = (C.c_void_p * max(self.n_ext, 1))()
+
+    def run(self, ext_ptrs):
+        """Issue the whole sequence on the tape's stream; ``ext_ptrs``: the device address of every external slot."""
+        assert len(ext_ptrs) == self.n_ext
+        for i, p in enumerate(ext_ptrs):
+            self._ext[i] = p or None
+        _check(self._lib.ctn_grad_tape_run(self._h, self._ext, self.n_ext))
+
+    def info(self):
+        out = (C.c_int64 * len(TAPE_INFO))()
+        _check(self._lib.ctn_grad_tape_info(self._h, out))
+        return dict(zip(TAPE_INFO, (int(v) for v in out)))
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.ctn_grad_tape_destroy(h)
+
+    def __del__(self):
+        self.close()
+
+
+def _dtype_code(dt):
+    return CTN_F32 if np.dtype(dt) == np.float32 else CTN_F64
+
+
+def tape_desc(records, slots, n_ext, n_regs, plans, max_bytes=None):
+    """``(ctn_tape_desc, arrays it points into)`` of a record list as `GradTape` takes it."""
+    recs = (TapeRecord * max(len(records), 1))()
+    dims, strides, first = [], [], []
+    for r, src in zip(recs, records):
+        r.kind, r.plan, r.out, r.aux = src["kind"], src.get("plan", -1), src["out"], src.get("aux", -1)
+        ins, regs = list(src["in"]), list(src["reg"])
+        for j in range(3):
+            r.in_[j] = ins[j] if j < len(ins) else -1
+        for j in range(4):
+            r.reg[j] = regs[j] if j < len(regs) else -1
+        r.src_dtype = _dtype_code(src["src_dtype"])
+        r.dst_dtype = _dtype_code(src.get("dst_dtype", src["src_dtype"]))
+        r.ndim, r.axes = len(src.get("dims", ())), len(dims)
+        dims += list(src.get("dims", ()))
+        strides += list(src.get("strides", ()))
+        first += list(src.get("first", ()))
+        r.numel, r.min_norm = int(src.get("numel", 0)), float(src.get("min_norm", 0.0))
+    sl = (TapeSlot * max(len(slots), 1))()
+    for dst, (ext, idx, nbytes) in zip(sl, slots):
+        dst.external, dst.ext_index, dst.bytes = int(ext), int(idx), int(nbytes)
+    pl = (C.c_void_p * max(len(plans), 1))(*[p._h.value for p in plans])
+    d_arr, s_arr, f_arr = _i64(dims + [0]), _i64(strides + [0]), _i32(first + [0])
+    desc = TapeDesc()
+    desc.n_records, desc.n_slots, desc.n_ext, desc.n_regs = len(records), len(slots), int(n_ext), int(n_regs)
+    desc.n_plans, desc.n_axes = len(plans), len(dims)
+    desc.records, desc.slots, desc.plans = recs, sl, pl
+    desc.leaf_dims, desc.leaf_strides, desc.leaf_first = _ptr(d_arr, C.c_int64), _ptr(s_arr, C.c_int64), _ptr(f_arr, C.c_int32)
+    if max_bytes is None:
+        max_bytes = int(os.environ.get("CTN_GRAD_TAPE_MAX_BYTES") or TAPE_MAX_BYTES)
+    desc.max_bytes = int(max_bytes)
+    return desc, (recs, sl, pl, d_arr, s_arr, f_arr)

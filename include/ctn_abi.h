@@ -379,6 +379,81 @@ int ctn_cplx_normalize(ctn_exec* exec, int dtype, const void* t_e, const void* c
 int ctn_cplx_normalize_grad(ctn_exec* exec, int dtype, const void* t, const void* g_t, const void* g_c,
                             const double* rho, int64_t numel, void* g_te, double* scratch);
 
+/*
+ * Backward tape: a whole reverse pass of contract() as a fixed sequence of records over fixed device
+ * buffers, issued by ONE call and, from its third run on, replayed as one hipGraph launch.  The records are exactly what
+ * the step-by-step walk of the host layer issues, in its order, so the results are the same bits.  (Like
+ * ctn_exec_step_form, these entry points leave CTN_ABI_VERSION as it is.)
+ *
+ * A SLOT names a buffer: an ARENA slot is `bytes` of the one device allocation the tape owns (placed by liveness, 16-byte
+ * aligned: nothing shares bytes with anything alive at the same time); an EXTERNAL slot is entry `ext_index` of the pointer
+ * array handed to every ctn_grad_tape_run - the operands, the incoming cotangents and the gradient destinations, which are
+ * different tensors on every call.  REGISTERS are float64 values in one block at the head of the arena, zeroed at the start
+ * of every run inside the replayed sequence.
+ *
+ * Records (slots and registers by index, -1 = none):
+ *   CTN_TAPE_RUN   enqueue one-step plan `plan` (eager rescale mode, an executor of its own) on in[0], in[1] (-1: unary)
+ *                  into `out`; then reg[0] = the run's log register and reg[1] = reg[0] + reg[2] + reg[3], added in
+ *                  that order (what ctn_exec_snapshot_scales and ctn_exec_add_scales do, as one launch of k_tape_regs).
+ *   CTN_TAPE_SEED  ctn_grad_seed: t_hat = in[0], g_hat = in[1], g_c = in[2], scratch = aux (an arena slot of
+ *                  CTN_GRAD_SCRATCH doubles), z = reg[0], g_in = reg[1], g_out = reg[2]; numel, min_norm; dtype = src_dtype.
+ *   CTN_TAPE_LEAF  ctn_grad_leaf: src = in[0], g = reg[0], dst = out; ndim axes described by entries
+ *                  [axes, axes + ndim) of the desc's leaf_dims / leaf_strides / leaf_first; src_dtype, dst_dtype.
+ * SEED and LEAF read every pointer from a device table of the slots' addresses that the tape refreshes before each run
+ * (outside the graph), so they are part of the replayed sequence like everything else; the pointer tables of the RUN
+ * records that touch an external slot are refreshed at the same point.  No host-to-device copy is issued under capture.
+ *
+ * ctn_grad_tape_create: CTN_UNSUPPORTED when the arena would exceed max_bytes (the caller then walks step by step),
+ *   CTN_INVALID_ARG for a sequence that reads an arena slot before it is written or whose indices leave their ranges.
+ *   `stream` must not be NULL.  Plans are borrowed and must outlive the tape.
+ * ctn_grad_tape_run: the first run is issued launch by launch, the second under hipStreamBeginCapture (thread-local mode)
+ *   and launched as a graph, later runs replay it.  Runs stay eager while the stream is being captured by someone else, for
+ *   good after a failed capture or instantiation, and always with CTN_GRAPH=0.  Like a ctn_exec, one thread at a time.
+ *   CTN_OOM / CTN_HIP_ERROR when the device refuses the arena or an executor: one executor per RUN record, each with
+ *   its own small device buffers, which max_bytes does NOT count.  A failed creation frees what it took and leaves no
+ *   HIP error pending, so the caller may walk instead.
+ * ctn_grad_tape_info: info[0..10) = records, arena bytes, executors, eager runs, captured runs, replayed runs,
+ *   bytes of the register block, slots, device bytes the creation took (arena, table and executors together, as the
+ *   free memory of the device fell), microseconds the creation took.
+ */
+typedef enum { CTN_TAPE_RUN = 0, CTN_TAPE_SEED = 1, CTN_TAPE_LEAF = 2 } ctn_tape_kind;
+typedef struct {
+  int32_t kind;      /* ctn_tape_kind */
+  int32_t plan;      /* RUN: index into ctn_tape_desc.plans */
+  int32_t in[3];
+  int32_t out;
+  int32_t aux;
+  int32_t reg[4];
+  int32_t src_dtype; /* ctn_dtype */
+  int32_t dst_dtype;
+  int32_t ndim;
+  int32_t axes;
+  int32_t reserved;
+  int64_t numel;
+  double min_norm;
+} ctn_tape_record;
+typedef struct {
+  int32_t external;  /* 0: arena, 1: external */
+  int32_t ext_index; /* external: index into the pointer array of ctn_grad_tape_run */
+  int64_t bytes;     /* arena: size (a multiple of the element size, > 0) */
+} ctn_tape_slot;
+typedef struct {
+  int32_t n_records, n_slots, n_ext, n_regs, n_plans, n_axes;
+  const ctn_tape_record* records;
+  const ctn_tape_slot* slots;
+  const ctn_plan* const* plans;
+  const int64_t* leaf_dims;    /* [n_axes] */
+  const int64_t* leaf_strides; /* [n_axes] */
+  const int32_t* leaf_first;   /* [n_axes] */
+  int64_t max_bytes;           /* refuse a larger arena */
+} ctn_tape_desc;
+typedef struct ctn_grad_tape ctn_grad_tape;
+#define CTN_TAPE_INFO 10
+int ctn_grad_tape_create(const ctn_tape_desc* desc, int device, void* stream, ctn_grad_tape** out);
+int ctn_grad_tape_run(ctn_grad_tape* tape, void* const* ext, int n_ext);
+int ctn_grad_tape_info(const ctn_grad_tape* tape, int64_t* info /* [CTN_TAPE_INFO] */);
+void ctn_grad_tape_destroy(ctn_grad_tape* tape);
+
 #ifdef __cplusplus
 }
 #endif

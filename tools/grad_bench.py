@@ -1,6 +1,8 @@
 """Backward cost of contract() on device tensors (contractn_amd/autograd.py), one MI355X.
 
-    python tools/grad_bench.py [--reps 5] [--warmup 2]
+    python tools/grad_bench.py [--reps 5] [--warmup 2] [--tape {0,1}] [--dtypes float32,float64] [--only NAME]
+    python tools/grad_bench.py --ab 5            # walk and backward tape alternated in one session, median and spread
+    python tools/grad_bench.py --tape 1 --only mps100_D256 --profile-iters 20      # under a kernel trace: K steps, no timing
 
 Per network: the no-grad forward, then forward + backward of a loss on ``(T_hat, c)``, both timed with torch events on
 the current stream (median of ``--reps``).  The backward's algorithmic work is taken as twice the forward plan's flops
@@ -10,7 +12,11 @@ TFLOP/s against the MFMA peak of the dtype.  Networks:
 * ``mps100_D256``: the 100-site D = 256 MPS overlap (fp32), one network;
 * ``mps100_D64_classifier``: a 100-site D = 64 batched-MPS classifier training step, B = 256 inputs (fp32);
 * ``readme_3x3_chain``: the README's 1000-matrix 3 x 3 chain (fp64, split format; its plain value is inf).
-One JSON line per network.
+One JSON line per network and dtype (``--dtypes``: every network cast to each; default its own).  ``--tape 1`` runs the
+backward as a backward tape (CTN_GRAD_TAPE=1: one native call, a graph replay from the third run on).  ``--ab N`` times
+forward + backward N times under each setting in turn - walk, tape, walk, ... - and reports per setting the median of
+the N medians and their spread (max - min); the warm-up of the first round carries the tape past its capture.  Both
+report under ``tapes`` what the tapes cost to create (executors, device bytes, milliseconds).
 """
 import argparse
 import json
@@ -40,6 +46,19 @@ def timed(torch, fn, reps, warmup):
     return float(np.median(ts))
 
 
+def tape_cost(AG):
+    """What the backward tapes alive now cost to create: records, executors, arena bytes, device bytes taken (arena,
+    table and executors together) and creation time, from ctn_grad_tape_info."""
+    out = []
+    for sch in list(AG._SCHEDULES.values()):
+        for hit in list(sch._tapes.values()):
+            if hit is not None:
+                i = hit[0].info()
+                out.append({"records": i["records"], "executors": i["executors"], "arena_bytes": i["arena_bytes"],
+                            "device_bytes": i["device_bytes"], "create_ms": round(i["create_us"] / 1e3, 1)})
+    return out
+
+
 def networks(torch):
     from contractn_amd import TN
     from contractn_amd.paths import ssa_to_linear
@@ -62,12 +81,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--tape", type=int, choices=(0, 1), default=None, help="CTN_GRAD_TAPE for the backward (default: as set)")
+    ap.add_argument("--dtypes", default="", help="comma-separated dtypes every network is cast to (default: its own)")
+    ap.add_argument("--only", default="", help="run this network only")
+    ap.add_argument("--ab", type=int, default=0, help="alternate walk and tape this many times, report median and spread")
+    ap.add_argument("--profile-iters", type=int, default=0, help="just this many forward + backward steps, nothing timed")
     args = ap.parse_args()
+    if args.tape is not None:
+        os.environ["CTN_GRAD_TAPE"] = str(args.tape)
     import torch
 
+    from contractn_amd import autograd as AG
     from contractn_amd import einsum as E
 
+    cases = []
     for name, einstr, arrays, path, trainable in networks(torch):
+        if args.only and name != args.only:
+            continue
+        for dt in ([d for d in args.dtypes.split(",") if d] or [str(arrays[0].dtype)]):
+            cases.append((name, einstr, [np.asarray(a, dtype=dt) for a in arrays], path, trainable))
+    for name, einstr, arrays, path, trainable in cases:
         ops = [torch.tensor(a, device="cuda") for a in arrays]
         dt = str(arrays[0].dtype)
         shapes = tuple(tuple(a.shape) for a in arrays)
@@ -87,6 +120,31 @@ def main():
             loss = t_hat.square().sum() + c
             torch.autograd.grad(loss, leaves)
 
+        if args.profile_iters:
+            AG.reset_backward_stats()
+            for _ in range(args.profile_iters):
+                fwd_bwd()
+            torch.cuda.synchronize()
+            print(json.dumps({"network": name, "dtype": dt, "steps": args.profile_iters, "backward": AG.backward_stats(),
+                              "tapes": tape_cost(AG)}),
+                  flush=True)
+            continue
+        if args.ab:
+            t_f = timed(torch, fwd, args.reps, args.warmup)
+            rounds = {"walk": [], "tape": []}
+            AG.reset_backward_stats()
+            for i in range(args.ab):
+                for mode in ("walk", "tape"):
+                    os.environ["CTN_GRAD_TAPE"] = "1" if mode == "tape" else "0"
+                    rounds[mode].append(timed(torch, fwd_bwd, args.reps, max(args.warmup, 3) if i == 0 else 1))
+            out = {"network": name, "dtype": dt, "forward_ms": round(t_f, 3), "reps": args.reps, "rounds": args.ab}
+            for mode, ts in rounds.items():
+                out[mode] = {"median_ms": round(float(np.median(ts)), 3), "spread_ms": round(max(ts) - min(ts), 3),
+                             "ratio": round(float(np.median(ts)) / t_f, 2), "rounds_ms": [round(t, 3) for t in ts]}
+            out["backward"] = AG.backward_stats()
+            out["tapes"] = tape_cost(AG)
+            print(json.dumps(out), flush=True)
+            continue
         t_f = timed(torch, fwd, args.reps, args.warmup)
         t_fb = timed(torch, fwd_bwd, args.reps, args.warmup)
         t_b = max(t_fb - t_f, 1e-6)
