@@ -38,6 +38,7 @@
 #include "kernels_mfma_ares.h"
 #include "kernels_zip.h"
 #include "kernels_zipq.h"
+#include "kernels_zipqp.h"
 #include "kernels_zip64.h"
 #include "kernels_zip128.h"
 #include "kernels_zipm64.h"
@@ -83,7 +84,11 @@ struct DevSwitches {
                          // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
                          // (k_zip_f64) whenever the pair matches; 2 has no fp64 meaning and keeps the two-launch path
   int zipq = -1;         // CTN_ZIPQ: 0 never the two-legs-per-pass form of the bond-256 pair (k_zipq_f32), 1 whenever the pair matches it
-                         // (zip_match and Q even - tests), unset: kZipQDefault where k_zip_f32 is taken by its own default rule
+                         // (zip_match and Q even - tests), 2 likewise its form that walks several work items per workgroup
+                         // (k_zipqp_f32), unset: kZipQDefault where k_zip_f32 is taken by its own default rule, and of the two
+                         // forms k_zipqp_f32 under kZipQPDefault from two rounds of workgroups on
+  int zipq_wgs = 0;      // CTN_ZIPQ_WGS=n: at most n workgroups per k_zipqp_f32 launch (1 ... CUs; tests and experiments: a small
+                         // launch crosses item seams only under a cap); never part of the default rule
   int zip128 = 1;        // CTN_ZIP128=0: never the bond-128 pair kernel (k_zip128_f32), which CTN_ZIP=1 takes for fp32 pairs with
                          // |m1| = |n2| = 128 that no bond-256 form matches
   int zipm64 = 1;        // CTN_ZIPM64=0: never the bond-64 pair kernel (k_zipm64_f32), which CTN_ZIP=1 takes for fp32 pairs with
@@ -120,6 +125,7 @@ static DevSwitches read_dev_switches() {
   d.hform = num("CTN_H", -1);
   d.zip = num("CTN_ZIP", -1);
   d.zipq = num("CTN_ZIPQ", -1);
+  d.zipq_wgs = num("CTN_ZIPQ_WGS", 0);
   d.zip128 = num("CTN_ZIP128", 1);
   d.zipm64 = num("CTN_ZIPM64", 1);
   d.zipl = num("CTN_ZIPL", -1);
@@ -190,9 +196,16 @@ struct Exec {
   struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
                    int zu = 128; bool f64 = false;      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
                    int zm = 256;
-                   bool zq = false; };                  // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even)                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
+                   bool zq = false, zqp = false; };     // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even); zqp: as k_zipqp_f32                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
   std::vector<ZipDesc> zip;
   std::vector<char> zip_skip;
+  // k_zipqp_f32 only: results that the plan's workspace puts where the pair's own E lies (the planner frees E at the
+  // pair's first step, and first fit hands its bytes to E') live in side buffers instead - zqp_side[id] = which one, or -1.
+  // A workgroup of k_zipq_f32 stores its rows of E' when every workgroup of the replica has long read E; a workgroup
+  // that goes on to the replica's next block of u has not.
+  char* d_zqp_side = nullptr;
+  std::vector<int> zqp_side;
+  int64_t zqp_side_bytes = 0;       // one replica's part of one side buffer
   // the same pairs in their latency form (kernels_zipl.h): zl[s2] = the fused launch of steps (s2 - 1, s2), whose result
   // leaves as slabs; from_prev = its E is the slabs of the pair before, feeds_next = the next pair adds its slabs up (else
   // k_zip_slab_sum does); zl_skip[s1] like zip_skip
@@ -301,7 +314,7 @@ struct Exec {
                     (void*)d_stepOff, (void*)d_stepSlots,
                     (void*)d_stage_in, (void*)d_stage_out, (void*)d_group_args, (void*)d_sweep_ids, (void*)d_sweep_off,
                     (void*)d_sweep_slots, (void*)d_sweep_a, (void*)d_sweep_s, (void*)d_sweep_z, (void*)d_sweep_la, (void*)d_sweep_ls, (void*)d_sweep_e,
-                    (void*)d_merge, (void*)d_zl_slab[0], (void*)d_zl_slab[1], (void*)d_mult, (void*)d_cplx_tabs, (void*)d_chain_prog})
+                    (void*)d_merge, (void*)d_zl_slab[0], (void*)d_zl_slab[1], (void*)d_mult, (void*)d_cplx_tabs, (void*)d_chain_prog, (void*)d_zqp_side})
       if (p) (void)hipFree(p);
     if (h_pack) (void)hipHostFree(h_pack);
     if (h_group_args) (void)hipHostFree(h_group_args);
@@ -699,6 +712,11 @@ static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_
 static constexpr bool kZipQDefault = true;
 // Can k_zipq_f32 run a pair that zip_match took for k_zip_f32?  Its legs go in pairs, and its LDS-DMA requests address
 // every operand with an unsigned 32-bit byte offset off the tensor's base.
+// Of the two forms of that kernel, is k_zipqp_f32 (a workgroup walks its work items; kernels_zipqp.h) taken without
+// CTN_ZIPQ=2 where the rule above takes k_zipq_f32 and the launch has two rounds of workgroups at least (fewer: nothing
+// to walk)?  Decided by measurement: +1.7 % on the headline at R = 512 (5,302.8 -> 5,391.9 contractions/s,
+// spreads 7.9 and 5.0: eleven times the larger), +2.0 % at R = 256; the same bits.
+static constexpr bool kZipQPDefault = true;
 static bool zipq_fits(const Exec::ZipDesc& z) {
   const int64_t lim = (int64_t)1 << 31;
   return z.Q >= 2 && z.Q % 2 == 0 && (int64_t)z.K1 * z.ldE * 4 < lim && ((int64_t)z.Q * z.ldXq + (int64_t)z.K1 * z.ldXk + z.U) * 4 < lim &&
@@ -1214,13 +1232,14 @@ static int exec_launch_steps(Exec* E) {
       z.partC = E->d_partials + (size_t)E->step_off[s] * R;
       z.partC_stride = E->step_partials[s];
       z.R = R; z.dbg = nullptr;
+      z.n_items = (int32_t)zipq_items(R, zd.U, zd.zu);
       const bool timed_z = E->timing_runs < E->timing_slots;
       const size_t ez = timed_z ? ((size_t)E->timing_runs * P.n_steps + s) * 2 : 0;
       if (timed_z) HIPCHECK(hipEventRecord(E->events[ez], E->stream));
       if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
       if ((int)E->launched_form.size() != P.n_steps) E->launched_form.assign(P.n_steps, 0);
       E->launched_form[s] = zd.f64 ? CTN_FORM_ZIP_F64 : zd.zm == Z4M ? CTN_FORM_ZIPM64 : zd.zm == Z1M ? CTN_FORM_ZIP128
-                            : zd.zu == 64 ? CTN_FORM_ZIP64 : zd.zq ? CTN_FORM_ZIPQ : CTN_FORM_ZIP;
+                            : zd.zu == 64 ? CTN_FORM_ZIP64 : zd.zqp ? CTN_FORM_ZIPQP : zd.zq ? CTN_FORM_ZIPQ : CTN_FORM_ZIP;
       // the fused pair: 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256):
       // an fp64 step with 128 tile columns reads as k_mfma_f64_g
       // k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a wave sums; k_zipm64_f32 (bond 64) likewise
@@ -1242,6 +1261,7 @@ static int exec_launch_steps(Exec* E) {
       else if (zd.zm == Z4M) hipLaunchKernelGGL(k_zipm64_f32, dim3((unsigned)((int64_t)per * R)), dim3(256), 0, E->stream, z);
       else if (zd.zm == Z1M) hipLaunchKernelGGL(k_zip128_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       else if (zd.zu == 64) hipLaunchKernelGGL(k_zip64_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
+      else if (zd.zqp) hipLaunchKernelGGL(k_zipqp_f32, dim3((unsigned)zipq_grid(z.n_items, E->n_cu, E->sw.zipq_wgs)), dim3(256), 0, E->stream, z);
       else if (zd.zq) hipLaunchKernelGGL(k_zipq_f32, dim3((unsigned)((int64_t)per * R)), dim3(256), 0, E->stream, z);
       else hipLaunchKernelGGL(k_zip_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
       if (E->eager_rescale && P.stabilize && s + 1 < P.n_steps) {
@@ -2067,8 +2087,14 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       else if (m128) { ok = true; z = z128; z.zu = ZU; }
       // the 128-u form with two legs per pass (k_zipq_f32): on request wherever the pair matches (CTN_ZIPQ=1, also where
       // the rules above chose otherwise - but not against CTN_ZIP=2), else under k_zip_f32's own default rule
-      if (E.sw.zipq == 1 && E.sw.zip != 2 && zip_match(P, s, &z128, CTN_F32) && zipq_fits(z128)) { ok = true; z = z128; z.zu = ZU; z.zq = true; }
-      else if (E.sw.zipq == -1 && kZipQDefault && E.sw.zip == -1 && ok && z.zu == ZU && f128 >= 0.9 && zipq_fits(z)) z.zq = true;
+      // ... and its walking form (k_zipqp_f32): on request (CTN_ZIPQ=2) wherever CTN_ZIPQ=1 takes k_zipq_f32, else under
+      // kZipQPDefault where that kernel is taken by default and has two rounds of workgroups at least
+      if ((E.sw.zipq == 1 || E.sw.zipq == 2) && E.sw.zip != 2 && zip_match(P, s, &z128, CTN_F32) && zipq_fits(z128)) {
+        ok = true; z = z128; z.zu = ZU; z.zq = true; z.zqp = E.sw.zipq == 2;
+      } else if (E.sw.zipq == -1 && kZipQDefault && E.sw.zip == -1 && ok && z.zu == ZU && f128 >= 0.9 && zipq_fits(z)) {
+        z.zq = true;
+        z.zqp = kZipQPDefault && zipq_items(replicas, z.U, ZU) >= 2 * (int64_t)E.n_cu;
+      }
       // bond 128 (k_zip128_f32: 128 values of u per workgroup, K1 a multiple of its tile depth and two tiles at least -
       // ZK = Z1K, as zip_match checks), when no bond-256 form matches: only on request (CTN_ZIP=1, and not CTN_ZIP128=0).
       // kZip128Default is where the rule of the other forms - at least one round of workgroups, rounds filled to 0.9 - would switch it on unasked;
@@ -2333,12 +2359,41 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       }
     }
   }
+  // k_zipqp_f32: a result that would overwrite the pair's E moves to a side buffer.  A buffer is free again once the
+  // step that consumes its tensor has been launched (every intermediate is consumed exactly once): a chain needs two.
+  if (!E.zip.empty()) {
+    const int64_t es = P.elem_size();
+    std::vector<int> busy_until;                        // per side buffer: the step that reads what it holds
+    for (int s = 1; s + 1 < P.n_steps; ++s) {
+      if (!E.zip[s].on || !E.zip[s].zqp) continue;
+      const int idE = P.steps[s - 1].lhs, idC = P.steps[s].out;
+      if (idE < P.n_inputs) continue;
+      const int64_t e0 = P.tensors[idE].ws_offset, e1 = e0 + P.tensors[idE].numel * es;
+      const int64_t c0 = P.tensors[idC].ws_offset, c1 = c0 + P.tensors[idC].numel * es;
+      const bool e_in_ws = E.zqp_side.empty() || E.zqp_side[idE] < 0;       // (an E that moved itself is out of the way)
+      if (!e_in_ws || c0 >= e1 || e0 >= c1) continue;
+      if (E.zqp_side.empty()) E.zqp_side.assign((size_t)E.n_tensors, -1);
+      int consumer = P.n_steps;
+      for (int c = s + 1; c < P.n_steps; ++c)
+        if (P.steps[c].lhs == idC || P.steps[c].rhs == idC || P.steps[c].lhs2 == idC) { consumer = c; break; }
+      int k = 0;
+      while (k < (int)busy_until.size() && busy_until[k] >= s - 1) ++k;      // (E's own buffer is read by step s - 1)
+      if (k == (int)busy_until.size()) busy_until.push_back(0);
+      busy_until[k] = consumer;
+      E.zqp_side[idC] = k;
+      E.zqp_side_bytes = std::max<int64_t>(E.zqp_side_bytes, (c1 - c0 + 255) / 256 * 256);
+    }
+    if (!busy_until.empty())
+      HIPCHECK_X(hipMalloc((void**)&E.d_zqp_side, (size_t)E.zqp_side_bytes * busy_until.size() * replicas));
+  }
   // pointer table: intermediates and the ones-scalar are fixed for the executor's lifetime
   E.h_ptrs.assign((size_t)replicas * E.n_tensors, nullptr);
   for (int r = 0; r < replicas; ++r) {
     void** row = E.h_ptrs.data() + (size_t)r * E.n_tensors;
     for (int id = P.n_inputs; id < P.n_inputs + P.n_steps - 1; ++id)
-      row[id] = E.d_ws + (size_t)r * P.ws_bytes_per_replica + P.tensors[id].ws_offset;
+      row[id] = E.zqp_side.empty() || E.zqp_side[id] < 0
+                    ? E.d_ws + (size_t)r * P.ws_bytes_per_replica + P.tensors[id].ws_offset
+                    : E.d_zqp_side + ((size_t)E.zqp_side[id] * replicas + r) * E.zqp_side_bytes;
     row[E.n_tensors - 1] = E.d_ones;
   }
 #undef HIPCHECK_X

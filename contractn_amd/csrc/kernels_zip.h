@@ -51,6 +51,7 @@ struct ZipArgs {
   double* partC;            // [R][partC_stride]: one partial per workgroup (U / 128 per replica)
   int32_t partC_stride, R;
   unsigned long long* dbg;  // CTN_STAMPS builds only
+  int32_t n_items;          // R U / 128: the work items k_zipqp_f32's workgroups walk (the other kernels: one per workgroup, unread)
 };
 
 constexpr int ZM = 256, ZU = 128, ZK = 16, ZSTG = 8192;   // stage: 8192 floats = 32 KiB

@@ -288,7 +288,7 @@ int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t*
 
 /*
  * Which fused zipper-pair kernel the LAST enqueue launched for `step` (read-only; measurement and tests).  Several forms
- * report the same tile - k_zip_f32 and k_zipq_f32 both (512, 256), "the 128-u throughput form" - and this tells them
+ * report the same tile - k_zip_f32, k_zipq_f32 and k_zipqp_f32 all (512, 256), "the 128-u throughput form" - and this tells them
  * apart.  CTN_FORM_NONE for every step that did not run as the launched (second) step of such a pair, and before the
  * first enqueue.  (An entry point added to the ABI leaves CTN_ABI_VERSION as it is: the version counts changes a
  * caller of the earlier entry points has to know about.)
@@ -300,7 +300,8 @@ typedef enum {
   CTN_FORM_ZIP64 = 3,   /* k_zip64_f32 */
   CTN_FORM_ZIP128 = 4,  /* k_zip128_f32 */
   CTN_FORM_ZIPM64 = 5,  /* k_zipm64_f32 */
-  CTN_FORM_ZIP_F64 = 6  /* k_zip_f64 */
+  CTN_FORM_ZIP_F64 = 6, /* k_zip_f64 */
+  CTN_FORM_ZIPQP = 7    /* k_zipqp_f32: k_zipq_f32 with a workgroup that walks several work items of the launch */
 } ctn_step_form;
 int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form);
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generates contractn_amd/csrc/kernels_zipq_asm.inc: the tiles of k_zipq_f32 (kernels_zipq.h) as inline-asm strings
-with the phase-1 accumulators pinned to the 256 AGPRs.
+with the phase-1 accumulators pinned to the 256 AGPRs - and kernels_zipqp_asm.inc, the same tiles for k_zipqp_f32
+(kernels_zipqp.h; `selfadv`: the statements also advance the request cursor from tile to tile).
 
 A tile is 128 MFMAs (8192 cycles of the matrix pipe) and one asm statement:
 
@@ -52,13 +53,18 @@ def next_reads(nxt, buf):
     return ["ds_read_b32 %%[f%d], %%[nY] offset:%d" % (10 * buf + nb, y_off(0, nb)) for nb in range(8)]
 
 
-def requests():
+def requests(selfadv=False):
+    """`selfadv`: the statement finishes the cursor's step itself - a fourth add per offset register (%[ja] behind
+    request 3, %[jb] behind request 7: the tile's step less the three row steps), so that between two tiles of one kind
+    the kernel has nothing to recompute (k_zipqp_f32)."""
     out = []
     for i in range(8):
         r, s = ("ra", "sa") if i < 4 else ("rb", "sb")
         lines = ["s_mov_b32 m0, %[m0b]" if i == 0 else "s_add_u32 m0, m0, 0x400", "s_nop 0",
                  "global_load_lds_dwordx4 %%[%s], %%[%s]" % (r, s)]
         inc = {0: "ia", 1: "ia", 2: "ia", 4: "ib1", 5: "ib2", 6: "ib1"}.get(i)
+        if selfadv and i in (3, 7):
+            inc = "ja" if i == 3 else "jb"
         if inc:
             lines.append("v_add_u32 %%[%s], %%[%s], %%[%s]" % (r, inc, r))
         if i == 0:
@@ -69,7 +75,7 @@ def requests():
     return out
 
 
-def tile(kind, nxt, first=False, q2=0, ms=0):
+def tile(kind, nxt, first=False, q2=0, ms=0, selfadv=False):
     mf, reads = [], {}          # MFMA texts; reads[i] = instructions behind MFMA i
     if kind == "P1":
         for kk in range(8):
@@ -95,7 +101,7 @@ def tile(kind, nxt, first=False, q2=0, ms=0):
                 reads[8 * ks] = next_reads(nxt, nx)
         per = 8
     assert len(mf) == NMFMA
-    req = dict(zip(REQ_AT, requests()))
+    req = dict(zip(REQ_AT, requests(selfadv)))
     out = []
     for i, m in enumerate(mf):
         out.append(m)
@@ -113,20 +119,27 @@ def macro(name, lines):
     return "#define %s \\\n%s\n" % (name, body)
 
 
-hdr = '''// GENERATED by tools/gen_zipq_asm.py - do not edit.  The tiles of k_zipq_f32 (kernels_zipq.h): 128 MFMAs each,
-// phase-1 accumulators in a[0:255], fragment reads, the tile barrier and the LDS-DMA requests at fixed places.
-'''
+def emit(fname, prefix, hdr, selfadv=False):
+    """One .inc file: the 19 tiles under `prefix`."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    dst = os.path.join(here, "..", "contractn_amd", "csrc", fname)
+    with open(dst, "w") as fh:
+        fh.write(hdr)
+        fh.write(macro(prefix + "_P1_FIRST", tile("P1", "P1", first=True, selfadv=selfadv)))
+        fh.write(macro(prefix + "_P1_MID", tile("P1", "P1", selfadv=selfadv)))
+        fh.write(macro(prefix + "_P1_LAST", tile("P1", "P2", selfadv=selfadv)))
+        for q2 in range(2):
+            for ms in range(8):
+                nxt = "P1" if (q2, ms) == (1, 7) else "P2"
+                fh.write(macro(prefix + "_P2_%d_%d" % (q2, ms), tile("P2", nxt, q2=q2, ms=ms, selfadv=selfadv)))
+        fh.write("#define " + prefix + "_CLOBBERS \\\n  " + ", \\\n  ".join(
+            ", ".join('"a%d"' % r for r in range(b, b + 16)) for b in range(0, 256, 16)) + "\n")
+    print("wrote", os.path.normpath(dst))
 
-here = os.path.dirname(os.path.abspath(__file__))
-dst = os.path.join(here, "..", "contractn_amd", "csrc", "kernels_zipq_asm.inc")
-with open(dst, "w") as fh:
-    fh.write(hdr)
-    fh.write(macro("CTN_ZQ_P1_FIRST", tile("P1", "P1", first=True)))
-    fh.write(macro("CTN_ZQ_P1_MID", tile("P1", "P1")))
-    fh.write(macro("CTN_ZQ_P1_LAST", tile("P1", "P2")))
-    for q2 in range(2):
-        for ms in range(8):
-            fh.write(macro("CTN_ZQ_P2_%d_%d" % (q2, ms), tile("P2", "P1" if (q2, ms) == (1, 7) else "P2", q2=q2, ms=ms)))
-    fh.write("#define CTN_ZQ_CLOBBERS \\\n  " + ", \\\n  ".join(
-        ", ".join('"a%d"' % r for r in range(b, b + 16)) for b in range(0, 256, 16)) + "\n")
-print("wrote", os.path.normpath(dst))
+
+emit("kernels_zipq_asm.inc", "CTN_ZQ", '''// GENERATED by tools/gen_zipq_asm.py - do not edit.  The tiles of k_zipq_f32 (kernels_zipq.h): 128 MFMAs each,
+// phase-1 accumulators in a[0:255], fragment reads, the tile barrier and the LDS-DMA requests at fixed places.
+''')
+emit("kernels_zipqp_asm.inc", "CTN_ZQP", '''// GENERATED by tools/gen_zipq_asm.py - do not edit.  The tiles of k_zipqp_f32 (kernels_zipqp.h): those of
+// kernels_zipq_asm.inc with a self-advancing request cursor (%[ja], %[jb]: the fourth add per offset register).
+''', selfadv=True)
