@@ -29,6 +29,7 @@
 #include "chain_pack.h"
 #include "cplx_match.h"
 #include "grad_tape.h"
+#include "launch_form.h"
 
 #include "kernel_args.h"
 #include "kernels_mfma.h"
@@ -60,100 +61,10 @@ namespace ctn {
 // ---------------------------------------------------------------------------
 thread_local std::string g_err;
 
-// Development switches: every environment variable the library looks at, read in ONE place, once per executor
-// (ctn_exec_create) - never on the launch path.  None is needed in production ("Development switches").
-struct DevSwitches {
-  int mfma_g = 1;        // CTN_MFMA_G: 0 never use the large-tile LDS-DMA kernels, 1 when a launch fills the chip, 2 whenever eligible (tests)
-  int graph = 1;         // CTN_GRAPH=0: every enqueue issues its launches one by one
-  int mfma_bk = 0;       // CTN_MFMA_BK=16|32: force the k-tile depth of k_mfma_f32
-  int group = 1;         // CTN_GROUP=0: never batch independent leaf steps into one launch (k_stream_group)
-  int halve = 1;         // CTN_HALVE_TILES=0: never halve the tiles of an under-filled register-staged launch
-  int lat_wg_per_cu_x2 = 2;  // CTN_LAT_WG_X2: twice the workgroups per CU up to which the one-launch latency form is taken
-  int lat_max_t = 64;    // CTN_LAT_MAX_T=32: no 64 x 64 form of the one-launch latency kernel
-  int splitk_fill_long = 2;  // CTN_SPLITK_FILL_LONG: K >= 1024 steps are split until 64 x 64 tiles give this many workgroups per CU
-  int lat64_min_k = 512; // CTN_LAT64_MIN_K: least K for the 64 x 64 one-launch latency form when an operand is k-contiguous
-  int splitk = -1;       // CTN_SPLITK: 0 disables the latency mode, 1 forces it for every eligible step (tests)
-  int splitk_max = 0;    // CTN_SPLITK_MAX: tile-count threshold of the latency mode
-  int lat = -1;          // CTN_LAT: 0 never use the one-launch latency form (k_mfma_f32_lat), 1 whenever the shape allows (tests)
-  int hform = -1;        // CTN_H: 0 never use the one-tile-per-CU form (k_mfma_f32_h), 1 whenever the shape allows (tests)
-  int sweep = -1;        // CTN_SWEEP: 0 never walk a chain of epilogue-summed steps in one launch (k_sweep_f32), 1 whenever one matches (tests)
-  int sweep64 = 1;       // CTN_SWEEP64=0: never the float64 sweep (k_sweep_f64), which CTN_SWEEP=1 takes on a float64 plan whose
-                         // per-site step pairs (a GEMM and the streaming sum over p) match
-  int dot_tr = 1;        // CTN_DOT_TR=0: full dots against a transposed tensor stay on k_dot_split's 4-byte gathers
-  int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches
-                         // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
-                         // (k_zip_f64) whenever the pair matches; 2 has no fp64 meaning and keeps the two-launch path
-  int zipq = -1;         // CTN_ZIPQ: 0 never the two-legs-per-pass form of the bond-256 pair (k_zipq_f32), 1 whenever the pair matches it
-                         // (zip_match and Q even - tests), 2 likewise its form that walks several work items per workgroup
-                         // (k_zipqp_f32), unset: kZipQDefault where k_zip_f32 is taken by its own default rule, and of the two
-                         // forms k_zipqp_f32 under kZipQPDefault from two rounds of workgroups on
-  int zipq_wgs = 0;      // CTN_ZIPQ_WGS=n: at most n workgroups per k_zipqp_f32 launch (1 ... CUs; tests and experiments: a small
-                         // launch crosses item seams only under a cap); never part of the default rule
-  int zip128 = 1;        // CTN_ZIP128=0: never the bond-128 pair kernel (k_zip128_f32), which CTN_ZIP=1 takes for fp32 pairs with
-                         // |m1| = |n2| = 128 that no bond-256 form matches
-  int zipm64 = 1;        // CTN_ZIPM64=0: never the bond-64 pair kernel (k_zipm64_f32), which CTN_ZIP=1 takes for fp32 pairs with
-                         // |m1| = |n2| = 64 (no bond-256 and no bond-128 form matches those)
-  int cplx = -1;         // CTN_CPLX: 1 a complex x complex step pair - the S step and the 4-byte-gather GEMM behind it - runs as one launch
-                         // (k_cmfma_f32) wherever cplx_match takes it; 0 or unset: never (kCplxDefault)
-  int chain = -1;        // CTN_CHAIN: 1 a chain plan is always walked by k_chain, 2 by k_chain_lds (records, inputs and intermediates
-                         // on chip) wherever chain_pack accepts the plan; unset: kChainLdsDefault
-  int zipl = -1;         // CTN_ZIPL: 0 never run a zipper pair as one latency-form launch (k_zip_lat), 1 whenever the pair matches (tests)
-  int zipl_max_r = 8;    // CTN_ZIPL_MAX_R: most networks in flight for which k_zip_lat is taken by default (100-site D = 256
-                         // network, ms per pass, k_zip_lat / per-step launches: R = 1 1.40 / 2.05, 2: 1.58 / 3.3, 4: 2.1 / 3.5,
-                         // 8: 4.1 / 4.4, 16: 8.5 / 7.0)
-  int g_big_min_k = 1024;  // CTN_G_BIG_MIN_K: least K from which full long-K steps of any width take the 256 x 256 tiles
-                           // (1536 until round 4; K = 1024, N = 1024: CP r = n = 1024 16.4 -> 15.9 ms, Tucker 15.8 -> 15.7 per mode product)
-  int ares = -1;         // CTN_ARES: 0 never the resident-left-operand kernel (k_mfma_f32_ares), 1 whenever the step's shape allows (tests)
-  int ares_ntw = 0;      // CTN_ARES_NTW: column tiles per workgroup of that kernel (tests)
-  int g_big = 1;         // CTN_G_BIG=0: never the 256 x 256 tiles (experiments)
-  int g_splitk = 1;      // CTN_G_SPLITK=0: no K split over workgroups on the large-tile kernel
-  int zipl_mp = 0;       // CTN_ZIPL_MP=32|64: force the part of m1 a k_zip_lat workgroup owns (tests)
-  bool g_no_asm = false; // CTN_G_NO_ASM: C++ inner loop instead of the hand-scheduled blocks
-  const char* stamps = nullptr;  // CTN_DEBUG_STAMPS=<file> (make STAMPS=1 builds): dump in-kernel cycle stamps
-  int stamp_step = -1;   // CTN_DEBUG_STAMP_STEP=<s>: stamp only this step
-};
-static DevSwitches read_dev_switches() {
-  DevSwitches d;
-  auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
-  d.mfma_g = num("CTN_MFMA_G", 1);
-  d.graph = num("CTN_GRAPH", 1);
-  const int bk = num("CTN_MFMA_BK", 0);
-  d.mfma_bk = (bk == 16 || bk == 32) ? bk : 0;
-  d.splitk = num("CTN_SPLITK", -1);
-  d.splitk_max = num("CTN_SPLITK_MAX", 0);
-  d.lat = num("CTN_LAT", -1);
-  d.hform = num("CTN_H", -1);
-  d.zip = num("CTN_ZIP", -1);
-  d.zipq = num("CTN_ZIPQ", -1);
-  d.zipq_wgs = num("CTN_ZIPQ_WGS", 0);
-  d.zip128 = num("CTN_ZIP128", 1);
-  d.zipm64 = num("CTN_ZIPM64", 1);
-  d.zipl = num("CTN_ZIPL", -1);
-  d.cplx = num("CTN_CPLX", -1);
-  d.chain = num("CTN_CHAIN", -1);
-  d.zipl_max_r = num("CTN_ZIPL_MAX_R", 8);
-  d.zipl_mp = num("CTN_ZIPL_MP", 0);
-  d.g_splitk = num("CTN_G_SPLITK", 1);
-  d.g_big = num("CTN_G_BIG", 1);
-  d.ares = num("CTN_ARES", -1);
-  d.ares_ntw = num("CTN_ARES_NTW", 0);
-  d.g_big_min_k = num("CTN_G_BIG_MIN_K", 1024);
-  d.dot_tr = num("CTN_DOT_TR", 1);
-  d.sweep = num("CTN_SWEEP", -1);
-  d.sweep64 = num("CTN_SWEEP64", 1);
-  d.lat64_min_k = num("CTN_LAT64_MIN_K", 512);
-  d.splitk_fill_long = num("CTN_SPLITK_FILL_LONG", 2);
-  d.lat_max_t = num("CTN_LAT_MAX_T", 64);
-  d.lat_wg_per_cu_x2 = num("CTN_LAT_WG_X2", 2);
-  d.halve = num("CTN_HALVE_TILES", 1);
-  d.group = num("CTN_GROUP", 1);
-  d.g_no_asm = getenv("CTN_G_NO_ASM") != nullptr;
-  d.stamps = getenv("CTN_DEBUG_STAMPS");
-  d.stamp_step = num("CTN_DEBUG_STAMP_STEP", -1);
-  return d;
-}
+static_assert(kFormGM == GM && kFormGK == GK && kFormDN == DN && kFormLatMaxK == kLatMaxK,
+              "launch_form.h selects kernels by these values of theirs");
 
-#define HIPCHECK(expr)                                                                   \
+#define HIPCHECK(expr)                                                                  \
   do {                                                                                   \
     hipError_t e_ = (expr);                                                              \
     if (e_ != hipSuccess) {                                                              \
@@ -184,7 +95,6 @@ struct Exec {
   int n_tensors = 0;
   int n_cu = 256;
   DevSwitches sw;        // environment switches as they were when the executor was created
-  int mfma_g = 1;        // sw.mfma_g (see exec_launch_steps)
   // the launch sequence as a hipGraph (CTN_GRAPH, see exec_launch_all): captured on the second enqueue,
   // replayed afterwards; tensors are reached through the device pointer table, so new operands need no update
   int use_graph = 1;
@@ -196,7 +106,8 @@ struct Exec {
   struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
                    int zu = 128; bool f64 = false;      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
                    int zm = 256;
-                   bool zq = false, zqp = false; };     // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even); zqp: as k_zipqp_f32                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
+                   bool zq = false, zqp = false;        // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even); zqp: as k_zipqp_f32                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
+                   int form = CTN_FORM_NONE; };         // the kernel that runs the pair (ctn_step_form), set where it is chosen
   std::vector<ZipDesc> zip;
   std::vector<char> zip_skip;
   // k_zipqp_f32 only: results that the plan's workspace puts where the pair's own E lies (the planner frees E at the
@@ -363,15 +274,6 @@ static void launch_mfma_epw(int ma, int mb, dim3 grid, hipStream_t st, const Ste
   }
 }
 
-// k-tile depth.  BK = 16: 32 KiB of LDS + 167 registers => 3 workgroups (12 waves) per CU, which
-// hides the per-tile prologue/epilogue best when K is short (MPS shapes: 108-118 TFLOP/s vs
-// 103-117 with BK = 32); BK = 32 halves the barriers per flop and wins on long-K GEMMs
-// (4096^3: 130 vs 115 TFLOP/s).  CTN_MFMA_BK=16|32 forces one of them (development knob).
-static int mfma_bk(int K, const DevSwitches& sw) {
-  if (sw.mfma_bk) return sw.mfma_bk;
-  return K >= 2048 ? 32 : 16;
-}
-
 // tile_m = 64: skinny rows (M <= 64 against a huge N) - always BK = 16 (these steps have a short K)
 static void launch_mfma(int ma, int mb, int tile_m, int tile_n, dim3 grid, hipStream_t st, const StepArgs& a, const DevSwitches& sw) {
   if (a.epw) {
@@ -397,171 +299,10 @@ static void launch_mfma(int ma, int mb, int tile_m, int tile_n, dim3 grid, hipSt
   }
 }
 
-// Latency mode (see k_mfma_f32_sk): chosen when the 128-wide tiles of a step cannot occupy half the
-// chip.  Returns the number of K splits (0 = use the throughput kernel).  CTN_SPLITK=0 disables,
-// CTN_SPLITK=1 forces it for every eligible step (tests).
-static bool h_forced(const Step& st, int dtype, const DevSwitches& sw);
-static int splitk_splits(const Step& st, int R, int n_cu, int dtype, const DevSwitches& sw) {
-  if (h_forced(st, dtype, sw)) return 0;
-  const int mode = sw.splitk;
-  const bool mfma = (dtype == CTN_F32 && st.kernel == CTN_KERNEL_MFMA_F32) || (dtype == CTN_F64 && st.kernel == CTN_KERNEL_MFMA_F64);
-  if (mode == 0 || !mfma || st.collapse || st.K < 128 || st.modeA >= 3 || st.epw) return 0;
-  const int max_tiles = sw.splitk_max;
-  const int64_t limit = max_tiles > 0 ? max_tiles : n_cu / 2;
-  if (mode != 1 && (int64_t)st.blocks * R > limit) return 0;
-  const int64_t tiles64 = st.Bt * ((st.M + 63) / 64) * ((st.N + 63) / 64) * R;
-  // 64 x 64 tiles that already give every CU a workgroup run un-split on the register-staged kernel: two K slabs plus
-  // the reduce pass lose to it (7 replicas of 256 x 1024 x 256: 5.3 ms per 100-site network against 4.35 at 8) - a long
-  // K (>= 1024) is still worth two slabs up to two workgroups per CU (16 x (256 x 256 x 1024): 7.02 -> 6.20 ms)
-  if (tiles64 >= (int64_t)n_cu * (st.K >= 1024 ? sw.splitk_fill_long : 1) && mode != 1) return 0;
-  int64_t S = (2 * (int64_t)n_cu + tiles64 - 1) / tiles64;   // aim at ~2 small workgroups per CU
-  S = std::max<int64_t>(1, std::min<int64_t>(S, st.K / 64));
-  // one split is no split: the register-staged kernel on halved tiles does the same work without slab and reduce pass
-  // (8 replicas of a 256 x 1024 x 256 step; CTN_SPLITK=1 keeps it for the tests)
-  if (S <= 1 && mode != 1) return 0;
-  return (int)S;
-}
-
-// One-launch latency form (k_mfma_f32_lat): K split over the eight waves of a workgroup instead of over
-// workgroups, no slabs and no reduce launch.  Returns the tile edge T (16, 32 or 64), 0 = not taken.
-// Same launch-size condition as split-K (the step's 128-wide tiles cannot occupy half the chip); the largest tile
-// that still gives every CU a workgroup (with one network in flight a 256 x 256 x 1024 step runs as 256 tiles of
-// 16 x 16: on 64 tiles of 32 x 32 three quarters of the matrix pipes idle and the step takes 14 us instead of ~6);
-// at most kLatMaxTiles tiles per replica (one abs-sum partial each), both k-offset tables in LDS.
-constexpr int kLatMaxTiles = kMaxPartials;
-static int lat_form(const Step& st, int R, int n_cu, int dtype, const DevSwitches& sw) {
-  if (h_forced(st, dtype, sw)) return 0;           // tests of the one-tile-per-CU form (CTN_H=1)
-  const bool f64 = dtype == CTN_F64 && st.kernel == CTN_KERNEL_MFMA_F64;
-  if (sw.lat == 0 || !(f64 || (dtype == CTN_F32 && st.kernel == CTN_KERNEL_MFMA_F32)) || st.rhs < 0 || st.modeA >= 3 || st.epw) return 0;
-  if (st.K > kLatMaxK || st.K < 32) return 0;
-  if (sw.mfma_g >= 2 && (f64 ? st.tileN == 128 : st.tileM == 256)) return 0;   // tests that force the large-tile kernels
-  if (sw.lat != 1 && ((int64_t)st.blocks * R > n_cu / 2 || st.K < 128)) return 0;
-  auto tiles = [&](int T) { return st.Bt * ((st.M + T - 1) / T) * ((st.N + T - 1) / T); };
-  const int64_t t16 = tiles(16), t32 = tiles(32), t64 = tiles(64);
-  // ... and not more than one workgroup per CU (a second round of 512-thread workgroups doubles the step): beyond
-  // that split-K / halved register-staged tiles win (100-site D = 256 network, R = 4: 3.49 vs 4.23 ms; R = 5: 5.33 vs
-  // 4.61; R = 6: 5.55 vs 4.79; R = 8: 5.83 vs 4.37)
-  auto fits = [&](int64_t t) { return t <= kLatMaxTiles && (sw.lat == 1 || t * R <= (int64_t)n_cu * sw.lat_wg_per_cu_x2 / 2); };
-  if (f64) return fits(t16) ? 16 : 0;     // fp64: 16 x 16 tiles (v_mfma_f64_16x16x4_f64) only
-  // (a k-contiguous operand reaches the fragment registers as 4-byte loads a row stride apart; with a short K split
-  // eight ways there is nothing to pipeline them behind: 1024 x 1024 x 256, A k-contiguous, took 27.8 us on 256 tiles
-  // of 64 x 64 against 23.7 us for the LDS-staged tiles with two K slabs - while the same tile count with both
-  // operands row-contiguous, 4 x (256 x 1024 x 256), is 6 % faster here than there)
-  const bool kcontig = st.modeA == 2 || st.modeB == 2;
-  // (... and with K = 1024 the plain 64 x 64 tiles win: 16 replicas of 256 x 256 x 1024, 7.53 -> 7.03 ms per network)
-  if (sw.lat_max_t >= 64 && t64 * R >= n_cu && fits(t64) && st.K <= 512 && (!kcontig || st.K >= sw.lat64_min_k)) return 64;
-  if (t32 * R >= n_cu && fits(t32)) return 32;
-  if (fits(t16)) return 16;
-  if (fits(t32)) return 32;
-  // half the CUs busy with 64 x 64 tiles still beats four K slabs plus a reduce pass (2 / 3 replicas of
-  // 256 x 1024 x 256: 3.47 -> 3.28 / 3.62 -> 3.44 ms per 100-site network)
-  if (sw.lat_max_t >= 64 && 2 * t64 * R >= n_cu && fits(t64) && st.K <= 256 && !kcontig) return 64;   // (a long K is better off split over workgroups)
-  return 0;
-}
-
-// CTN_H=1 (tests): a step whose SHAPE admits the one-tile-per-CU form takes it whatever the launch size - the latency
-// forms step aside (the remaining conditions - vector-storable C, not the last step - are checked by h_form itself)
-static bool h_forced(const Step& st, int dtype, const DevSwitches& sw) {
-  return sw.hform == 1 && dtype == CTN_F32 && st.kernel == CTN_KERNEL_MFMA_F32 && st.rhs >= 0 && !st.collapse &&
-         st.modeA >= 1 && st.modeA <= 2 && st.modeB >= 1 && st.modeB <= 2 && st.K % 32 == 0 && st.K >= 64 && st.cvec &&
-         (st.epw ? (st.epw_split && (st.epw == 2 || st.epw == 4)) : st.lhs2 < 0) &&
-         st.Bt * ((st.M + 127) / 128) * ((st.N + 127) / 128) <= kMaxPartials;
-}
-
-// One-tile-per-CU form (k_mfma_f32_h, kernels_mfma_h.h): 128 x 128 tiles, K split over the two halves of an 8-wave
-// workgroup.  Taken when the step's 128 x 128 tiles are about one round of one workgroup per CU - between three quarters
-// of a chip and a whole one - which is where the register-staged kernel's 128 x 64 tiles run as a single round of two small
-// workgroups per CU and the large-tile kernel would leave CUs idle (one MPS site applied to 4096 inputs: 256 tiles).
-static bool h_form(const Plan& P, const Step& st, int R, int n_cu, int dtype, const DevSwitches& sw, bool c_vec) {
-  if (sw.hform == 0 || dtype != CTN_F32 || st.kernel != CTN_KERNEL_MFMA_F32 || st.rhs < 0 || st.collapse) return false;
-  if (st.modeA < 1 || st.modeA > 2 || st.modeB < 1 || st.modeB > 2) return false;      // LDS-DMA: 16-byte requests only
-  if (st.epw ? !(st.epw_split && (st.epw == 2 || st.epw == 4)) : st.lhs2 >= 0) return false;
-  if (st.K % 32 != 0 || st.K < 64 || !c_vec) return false;
-  if (P.tensors[st.lhs].numel > (1LL << 30) || P.tensors[st.rhs].numel > (1LL << 30)) return false;   // 32-bit byte offsets
-  const int64_t t128 = st.Bt * ((st.M + 127) / 128) * ((st.N + 127) / 128);
-  if (t128 > kMaxPartials) return false;
-  if (sw.hform == 1) return true;
-  if (sw.mfma_g >= 2 && st.tileM == 256) return false;     // tests that force the large-tile kernels
-  // (from three quarters of a chip of tiles: at half a chip - 8 networks of the headline in flight, 2048 inputs through
-  // the batched MPS - the smaller tiles of the other forms keep more CUs busy: 27.1 vs 20.6 us per site at B = 2048)
-  return 4 * t128 * R >= 3 * n_cu && t128 * R <= n_cu;
-}
-
-// Tile of the register-staged fp32 kernel for this step and replica count: the planner's 128 / 64 choice, halved
-// (rows or columns, the larger extent first) while the launch has fewer than two workgroups per CU - one network with
-// a batch leg, or a fused step whose output is a quarter of the GEMM it replaced - as long as the tile count still
-// fits the step's partial-sum region.  Steps the planner made eligible for the large-tile kernel keep 128-unit
-// counting (their fallback must agree with it), and so do steps that already go through the collapse pass.
-static bool g_launch(const Step& st, int R, int n_cu, int use_g) {
-  // does a launch of this (planner-eligible) step take the large-tile LDS-DMA kernel?  At least two of the big tiles
-  // per CU and K >= 192 (below that the 128-tile kernel's 3-4 workgroups per CU hide the per-tile cost better), or a
-  // long K (>= 1024) from 7/8 of a tile per CU; CTN_MFMA_G=2: whenever eligible (tests)
-  if (!use_g || st.kernel != CTN_KERNEL_MFMA_F32 || st.tileM != 256) return false;
-  const int64_t gtiles = st.Bt * ((st.M + 255) / 256) * ((st.N + st.tileN - 1) / st.tileN) * R;
-  if (use_g >= 2 || (gtiles >= 2LL * n_cu && st.K >= 192)) return true;
-  // ... below two tiles per CU a long K still pays, provided the tiles divide evenly over the CUs: 320 tiles are two
-  // rounds on 64 CUs and one on the rest (100-site network: 160 replicas 42.8 ms against 39.7 on 128-wide tiles; 96
-  // replicas = 192 tiles 25.2 against 23.1; 112 = 224 tiles 28.4 against 29.7, 128 = 256 tiles 29.0 against 29.1)
-  const int64_t rounds = (gtiles + n_cu - 1) / n_cu;
-  return st.K >= 1024 && 4 * gtiles >= 3LL * n_cu && 100 * gtiles >= 85 * rounds * n_cu;
-}
-
-// K split over workgroups ON the large-tile LDS-DMA kernel (256 x 128 tiles; k_mfma_f32_g with a.ks_S > 0, then the
-// fixed-order reduce pass): a planner-eligible step whose tiles cannot fill the chip by themselves while K is long - the
-// root GEMMs of a sliced 2D grid with a rank's few slices in flight (8 x (512 x 512 x 4096): 64 tiles; they ran as 512
-// register-staged 64 x 64 tiles), a batch of 256 x 256 x 2^20 products.  Returns the number of splits (0 = not taken): about
-// two workgroups per CU, every split at least 256 deep and a whole number of 16-deep k-tiles.
-static int g_splitk(const Step& st, int R, int n_cu, int use_g, const DevSwitches& sw, bool c_vec) {
-  if (!use_g || sw.g_splitk == 0 || st.kernel != CTN_KERNEL_MFMA_F32 || st.tileM != 256 || !c_vec || st.collapse || st.rhs < 0) return 0;
-  if (st.K < 2048 || st.K % GK != 0) return 0;
-  const int64_t gtiles = st.Bt * ((st.M + GM - 1) / GM) * ((st.N + st.tileN - 1) / st.tileN) * R;
-  if (gtiles >= n_cu) return 0;
-  int64_t S = (2LL * n_cu + gtiles - 1) / gtiles;
-  S = std::min<int64_t>(std::min<int64_t>(S, 16), st.K / 256);   // (at most 16 slabs: one reduce pass, no folding)
-  while (S > 1 && (st.K % S != 0 || (st.K / S) % GK != 0)) --S;
-  return S >= 2 ? (int)S : 0;
-}
-
-static void plain_tiles(const Step& st, int R, int n_cu, int use_g, bool is_last, int* tm, int* tn, int halve = 1) {
-  *tm = st.tileM == 64 ? 64 : kTileM;
-  *tn = st.tileN;
-  if (st.kernel != CTN_KERNEL_MFMA_F32 || st.collapse || !halve) return;
-  // a step the planner made eligible for the large-tile kernel keeps 128-unit counting when that kernel will (or,
-  // for the caller's possibly unaligned final buffer, may) take it
-  if (st.tileM == 256 && (is_last || g_launch(st, R, n_cu, use_g))) return;
-  auto tiles = [&](int a, int b) { return st.Bt * ((st.M + a - 1) / a) * ((st.N + b - 1) / b); };
-  while (tiles(*tm, *tn) * R < 2LL * n_cu) {
-    int a = *tm, b = *tn;
-    // columns first: 128 x 64 tiles measured 62 vs 45 TFLOP/s for 64 x 128 on 4096 x 1024 x 256 (one batched-MPS site)
-    if (b == 128 && st.N > 64) b = 64;
-    else if (a == 128 && st.M > 64) a = 64;
-    else break;
-    if (tiles(a, b) > 4096) break;
-    *tm = a; *tn = b;
-  }
-}
-
 // the reduce pass of a split-K step: fold 16 to 1 while more than 16 slabs are left (ping-pong between the two
 // slab buffers), then the final pass (rescale, C, abs-sum partials)
 template <typename T>
 static void launch_splitk_reduce(Exec* E, int partials, int R, const StepArgs& a, SplitKArgs sk);
-
-// A streaming step with few output items and a long K (column sums, `ab,ab->b`: 4 workgroups walked K = 4096 one
-// element at a time - 1.7 ms for 67 MB): split K over workgroups, partial sums through the split-K reduce pass
-static int stream_splits(const Step& st, int R, int n_cu) {
-  if (st.kernel != CTN_KERNEL_ELEMENT || st.K < 1024 || st.kvec) return 0;
-  const int64_t wgs = (int64_t)st.blocks * R;
-  if (wgs >= 2LL * n_cu) return 0;
-  return (int)std::max<int64_t>(2, std::min<int64_t>(std::min<int64_t>(st.K / 128, 1024), (8LL * n_cu + wgs - 1) / wgs));
-}
-
-// k_stream variant of a plain streaming step: vector width along n and vectors per row lookup (4 only where it pays:
-// short K - lookup-dominated - and enough rows left to fill the chip; long-K / small steps keep one for parallelism)
-static void stream_variant(const Step& st, int R, int vw, int* u, int64_t* nq) {
-  *nq = (st.Nv + vw - 1) / vw;
-  const int64_t rows = st.H * st.L * (int64_t)R;
-  *u = (*nq % 4 == 0 && st.K <= 16 && rows * (*nq / 4) >= (1 << 20)) ? 4 : 1;
-}
 
 template <typename T>
 static void launch_stream_group(int vw, int u, dim3 g, hipStream_t st, const StepArgs* arr) {
@@ -573,20 +314,6 @@ static void launch_stream_group(int vw, int u, dim3 g, hipStream_t st, const Ste
     if (u == 4) hipLaunchKernelGGL((k_stream_group<T, 1, 4>), g, dim3(256), 0, st, arr);
     else hipLaunchKernelGGL((k_stream_group<T, 1, 1>), g, dim3(256), 0, st, arr);
   }
-}
-
-// Row-dot steps (one wave per output) with few outputs and a long K: split K over workgroups too
-static int rowdot_splits(const Step& st, int R, int n_cu) {
-  if (st.kernel != CTN_KERNEL_ROWDOT || st.K < 4096) return 0;
-  const int64_t waves = st.H * st.L * st.Nv * (int64_t)R;
-  if (waves >= 16LL * n_cu) return 0;
-  return (int)std::max<int64_t>(2, std::min<int64_t>(std::min<int64_t>(st.K / 1024, 1024), (16LL * n_cu + waves - 1) / waves));
-}
-
-// Tiny output, huge K (CTN_KERNEL_DOT: at most 64 outputs): split K over workgroups as well, see k_dot_split
-static int dot_splits(const Step& st) {
-  if (st.kernel != CTN_KERNEL_DOT || st.K < 32768) return 0;
-  return (int)std::min<int64_t>(1024, st.K / 8192);
 }
 
 template <int MA>
@@ -994,759 +721,684 @@ static bool ares_avec(const Plan& P, int s) {
   return true;
 }
 
-static int exec_launch_steps(Exec* E) {
+// ---------------------------------------------------------------------------
+// the launch path: exec_launch_steps walks the plan and hands every step to the launch_<form> of its form.  Its helpers
+// are plain functions and small structs: nothing here allocates host memory.
+// ---------------------------------------------------------------------------
+static int record_event(Exec* E, size_t i) {
+  HIPCHECK(hipEventRecord(E->events[i], E->stream));
+  return CTN_OK;
+}
+
+// The timing bracket of step s (only the first `timing_slots` enqueues are bracketed): the first event is recorded when
+// the bracket is built - check rc -, the second by end().
+struct StepTimer {
+  Exec* E;
+  bool on;
+  size_t ev;
+  int rc;
+  StepTimer(Exec* E_, int s)
+      : E(E_), on(E_->timing_runs < E_->timing_slots), ev(on ? ((size_t)E_->timing_runs * E_->plan->n_steps + s) * 2 : 0),
+        rc(on ? record_event(E_, ev) : CTN_OK) {}
+  int end() const { return on ? record_event(E, ev + 1) : CTN_OK; }
+};
+
+// a step that launches nothing: an empty bracket
+static int time_nothing(Exec* E, int s) {
+  const StepTimer t(E, s);
+  return t.rc != CTN_OK ? t.rc : t.end();
+}
+
+// ... because it runs inside the next launched step (the first step of a pair, a member of a sweep): the marker tile too
+static int mark_absorbed(Exec* E, int s) {
+  E->launched_tile[s] = (1 << 16) | 1;
+  return time_nothing(E, s);
+}
+
+static void report_tile(Exec* E, int s, int tm, int tn) { E->launched_tile[s] = (tm << 16) | tn; }
+
+// step s's region of the partial sums, and its slots per replica
+static double* part_region(Exec* E, int s) { return E->d_partials + (size_t)E->step_off[s] * E->R; }
+
+// The partials of tensor `id`'s producer - unless the tensor is a network input (or absent), carries scale 1 (eager
+// mode: normalised in place), or was never written (CTN_KERNEL_FUSED)
+static void producer_partials(Exec* E, int id, const double** p, int32_t* cnt, int32_t* stride, double* numel) {
+  const Plan& P = *E->plan;
+  *p = nullptr; *cnt = 0; *stride = 0; *numel = 1;
+  if (id >= P.n_inputs && P.stabilize && !E->eager_rescale && P.steps[P.tensors[id].producer].kernel != CTN_KERNEL_FUSED) {
+    const int ps = P.tensors[id].producer;
+    *p = part_region(E, ps);
+    *cnt = *stride = E->step_partials[ps];
+    *numel = (double)P.tensors[id].numel;
+  }
+}
+
+// CTN_DEBUG_STAMPS: the stamp buffer for a launch of `need` workgroups, zeroed, into *dbg (untouched when step s is not stamped)
+static int stamp_buffer(Exec* E, int s, size_t need, unsigned long long** dbg) {
+  if (!E->sw.stamps || (E->sw.stamp_step >= 0 && E->sw.stamp_step != s)) return CTN_OK;
+  if (E->dbg_tiles < need) {
+    if (E->d_dbg) (void)hipFree(E->d_dbg);
+    HIPCHECK(hipMalloc((void**)&E->d_dbg, need * 64));
+    E->dbg_tiles = need;
+  }
+  *dbg = E->d_dbg;
+  HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
+  return CTN_OK;
+}
+
+static void launch_renorm(Exec* E, int s);
+
+// the arguments every kernel of a plain step takes, as the planner's own launch of the step would have them
+static void fill_step_args(Exec* E, int s, StepArgs* args) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  StepArgs& a = *args;
+  const int32_t* T = E->d_tables;
+  const int64_t* T8 = E->d_tables64;
+  a.obA = T8 + st.t.obA; a.obB = T8 + st.t.obB; a.obC = T8 + st.t.obC;
+  a.omA = T + st.t.omA; a.omC = T + st.t.omC;
+  a.onB = T + st.t.onB; a.onC = T + st.t.onC;
+  a.okA = T + st.t.okA; a.okB = T + st.t.okB;
+  a.ptrs = E->d_ptrs;
+  producer_partials(E, st.lhs, &a.partA, &a.PA, &a.strideA, &a.numelA);
+  producer_partials(E, st.rhs, &a.partB, &a.PB, &a.strideB, &a.numelB);
+  producer_partials(E, st.lhs2, &a.partA2, &a.PA2, &a.strideA2, &a.numelA2);
+  a.obA2 = T8 + st.t.obA2; a.omA2 = T + st.t.omA2; a.okA2 = T + st.t.okA2;
+  a.idA2 = st.lhs2 >= 0 ? st.lhs2 : E->n_tensors - 1;
+  a.krX = st.krX; a.krY = st.krY;
+  a.epw = st.epw | (st.epw_split ? 0x100 : 0);
+  // more workgroup partials than slots: through the scratch buffer and k_collapse
+  a.partC = st.collapse ? E->d_scratch : part_region(E, s);
+  a.partC_stride = st.collapse ? st.blocks : E->step_partials[s];
+  a.min_norm = P.min_norm;
+  a.Bt = (int32_t)st.Bt; a.M = (int32_t)st.M; a.N = (int32_t)st.N; a.K = (int32_t)st.K;
+  a.idA = st.lhs; a.idB = st.rhs >= 0 ? st.rhs : E->n_tensors - 1; a.idC = st.out;
+  a.n_tensors = E->n_tensors;
+  const int row_tile = (st.kernel == CTN_KERNEL_MFMA_F32 && st.tileM == 64) ? 64 : kTileM;
+  a.tiles_m = (int32_t)((st.M + row_tile - 1) / row_tile);
+  a.tiles_n = (int32_t)((st.N + kTileN - 1) / kTileN);
+  a.blocks_per_replica = st.blocks;
+  a.R = E->R;
+  a.c_vec = (st.cvec && (s + 1 < P.n_steps || E->outs_aligned16)) ? 1 : 0;
+  a.dbg = nullptr;
+  a.ks_slab = nullptr; a.ks_numelC = 0; a.ks_S = 0; a.ks_chunk = 0;
+  a.ohA = T8 + st.t.ohA; a.ohB = T8 + st.t.ohB; a.ohC = T8 + st.t.ohC;
+  a.olA = T + st.t.olA; a.olB = T + st.t.olB; a.olC = T + st.t.olC;
+  a.H = (int32_t)st.H; a.L = (int32_t)st.L; a.Nv = (int32_t)st.Nv;
+  a.sAn = (int32_t)st.sAn; a.sBn = (int32_t)st.sBn;
+  a.dNq = make_fastdiv((st.Nv + st.vecw - 1) / st.vecw);
+  a.dL = make_fastdiv(st.L);
+  a.dNv = make_fastdiv(st.Nv);
+}
+
+// a chain plan: the whole walk is one launch, timed as "step 0"
+static int launch_chain(Exec* E) {
   const Plan& P = *E->plan;
   const int R = E->R;
-  const bool chain = P.chain && E->d_chain != nullptr;
-  if (chain) {
-    const bool timed = E->timing_runs < E->timing_slots;
-    const size_t ev0 = timed ? (size_t)E->timing_runs * P.n_steps * 2 : 0;
-    if (timed) {
-      HIPCHECK(hipEventRecord(E->events[ev0], E->stream));
-    }
-    if (E->d_chain_prog && P.dtype == CTN_F32)
-      hipLaunchKernelGGL(k_chain_lds<float>, dim3(R), dim3(256), 0, E->stream, (const int32_t*)E->d_chain_prog, E->chain_len0, P.n_steps,
-                         (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
-    else if (E->d_chain_prog)
-      hipLaunchKernelGGL(k_chain_lds<double>, dim3(R), dim3(256), 0, E->stream, (const int32_t*)E->d_chain_prog, E->chain_len0, P.n_steps,
-                         (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
-    else if (P.dtype == CTN_F32)
-      hipLaunchKernelGGL(k_chain<float>, dim3(R), dim3(256), 0, E->stream, (const ChainStep*)E->d_chain, P.n_steps,
-                         (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
-    else
-      hipLaunchKernelGGL(k_chain<double>, dim3(R), dim3(256), 0, E->stream, (const ChainStep*)E->d_chain, P.n_steps,
-                         (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
-    if (timed) HIPCHECK(hipEventRecord(E->events[ev0 + 1], E->stream));  // whole walk = "step 0"
-  }
-  int group_skip = 0, collect_left = 0, collect_head = -1;
-  for (int s = 0; s < P.n_steps && !chain; ++s) {
-    const Step& st = P.steps[s];
-    if (group_skip > 0) { --group_skip; continue; }   // went out with the head of its group
-    if (collect_left == 0 && !E->groups.empty() && E->groups[s].len >= 2 && E->sw.group && !E->eager_rescale &&
-        !(E->timing_runs < E->timing_slots)) {
-      Exec::LeafGroup& G = E->groups[s];
-      if (G.ready) {
-        const dim3 g(G.blocks, R, G.len);
-        if (P.dtype == CTN_F32) launch_stream_group<float>(G.vw, G.u, g, E->stream, E->d_group_args + G.off);
-        else launch_stream_group<double>(G.vw, G.u, g, E->stream, E->d_group_args + G.off);
-        group_skip = G.len - 1;
-        continue;
-      }
-      collect_left = G.len; collect_head = s;   // first time: the steps' arguments are built below, not launched
-    }
-    if (!E->sweep_role.empty() && E->sweep_role[s] && !E->eager_rescale) {
-      if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-      const bool timed_w = E->timing_runs < E->timing_slots;
-      const size_t ew = timed_w ? ((size_t)E->timing_runs * P.n_steps + s) * 2 : 0;
-      if (timed_w) HIPCHECK(hipEventRecord(E->events[ew], E->stream));
-      if (E->sweep_role[s] == 1) {
-        E->launched_tile[s] = (1 << 16) | 1;        // marker: absorbed into the next launched step
-      } else if (E->sweep.f64) {                    // the last member of a float64 sweep: 2 S member steps, S sites
-        const Exec::SweepDesc& sd = E->sweep;
-        const int S = (int)sd.steps.size() / 2;
-        Sweep64Args w{};
-        w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
-        w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M;
-        w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
-        w.partIn = nullptr; w.PIn = 0; w.strideIn = 0; w.numelIn = 1.0;
-        if (sd.idIn >= P.n_inputs && P.stabilize && P.steps[P.tensors[sd.idIn].producer].kernel != CTN_KERNEL_FUSED) {
-          const int ps = P.tensors[sd.idIn].producer;
-          w.partIn = E->d_partials + (size_t)E->step_off[ps] * R;
-          w.PIn = w.strideIn = E->step_partials[ps];
-          w.numelIn = (double)P.tensors[sd.idIn].numel;
-        }
-        w.min_norm = P.min_norm;
-        w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
-        E->launched_tile[s] = (SWR << 16) | (sd.D * sd.Pd);   // 16 rows x all columns of C per workgroup, every site
-        {
-          const dim3 gs((unsigned)sd.J, (unsigned)R);
-#define CTN_SWEEP64_LAUNCH(DD)                                                                                              \
-          do {                                                                                                              \
-            if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_f64<DD, 4>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);      \
-            else hipLaunchKernelGGL((k_sweep_f64<DD, 2>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);                 \
-          } while (0)
-          if (sd.D == 64) CTN_SWEEP64_LAUNCH(64);
-          else if (sd.D == 128) CTN_SWEEP64_LAUNCH(128);
-          else if (sd.D == 256) CTN_SWEEP64_LAUNCH(256);
-          else CTN_SWEEP64_LAUNCH(512);
-#undef CTN_SWEEP64_LAUNCH
-        }
-        const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
-        hipLaunchKernelGGL(k_sweep64_z, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
-                           (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
-        Sweep64Finish f{};
-        f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
-        f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
-        f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
-        f.min_norm = P.stabilize ? P.min_norm : INFINITY;
-        hipLaunchKernelGGL(k_sweep64_finish, dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
-      } else {                                      // the last member: the whole chain, then its scale bookkeeping
-        const Exec::SweepDesc& sd = E->sweep;
-        const int S = (int)sd.steps.size();
-        const Step& f0 = P.steps[sd.steps.front()];
-        SweepArgs w{};
-        w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
-        w.idIn = f0.lhs; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M;
-        w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
-        w.partIn = nullptr; w.PIn = 0; w.strideIn = 0; w.numelIn = 1.0;
-        if (f0.lhs >= P.n_inputs && P.stabilize && P.steps[P.tensors[f0.lhs].producer].kernel != CTN_KERNEL_FUSED) {
-          const int ps = P.tensors[f0.lhs].producer;
-          w.partIn = E->d_partials + (size_t)E->step_off[ps] * R;
-          w.PIn = w.strideIn = E->step_partials[ps];
-          w.numelIn = (double)P.tensors[f0.lhs].numel;
-        }
-        w.min_norm = P.min_norm;
-        w.rec_a = E->d_sweep_a; w.rec_s = E->d_sweep_s; w.dbg = nullptr;
-        E->launched_tile[s] = (SWR << 16) | (sd.D * sd.Pd);   // 16 rows x all columns (1024 at bond 256, d = 4) per workgroup, every site
-        if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
-          const size_t need = (size_t)sd.J * R;
-          if (E->dbg_tiles < need) {
-            if (E->d_dbg) (void)hipFree(E->d_dbg);
-            HIPCHECK(hipMalloc((void**)&E->d_dbg, need * 64));
-            E->dbg_tiles = need;
-          }
-          w.dbg = E->d_dbg;
-          HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
-        }
-        {
-          const dim3 gs((unsigned)sd.J, (unsigned)R);
-#define CTN_SWEEP_LAUNCH(DD)                                                                                   \
-          do {                                                                                                 \
-            if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_f32<DD, 4>), gs, dim3(DD == 64 ? 256 : 512), 0, E->stream, w);  \
-            else hipLaunchKernelGGL((k_sweep_f32<DD, 2>), gs, dim3(DD == 64 ? 256 : 512), 0, E->stream, w);            \
-          } while (0)
-          if (sd.D == 64) CTN_SWEEP_LAUNCH(64);
-          else if (sd.D == 128) CTN_SWEEP_LAUNCH(128);
-          else if (sd.D == 256) CTN_SWEEP_LAUNCH(256);
-          else CTN_SWEEP_LAUNCH(512);
-#undef CTN_SWEEP_LAUNCH
-        }
-        const double numel = (double)P.tensors[st.out].numel;
-        hipLaunchKernelGGL(k_sweep_logs, dim3((unsigned)S, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
-                           (const float*)E->d_sweep_s, S, sd.J, E->d_sweep_la, E->d_sweep_ls);
-        hipLaunchKernelGGL(k_sweep_z, dim3((unsigned)S, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_la,
-                           (const double*)E->d_sweep_ls, S, sd.J, numel, E->d_sweep_z);
-        SweepFinish f{};
-        f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
-        f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.ls = E->d_sweep_ls; f.part_off = E->d_sweep_off;
-        f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numel = numel;
-        f.min_norm = P.stabilize ? P.min_norm : INFINITY;
-        hipLaunchKernelGGL(k_sweep_finish, dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
-      }
-      if (timed_w) HIPCHECK(hipEventRecord(E->events[ew + 1], E->stream));
-      continue;
-    }
-    if (!E->zl_skip.empty() && E->zl_skip[s]) {     // first step of a zipper pair in its latency form (k_zip_lat)
-      if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-      E->launched_tile[s] = (1 << 16) | 1;          // marker: absorbed into the next launched step
-      if (E->timing_runs < E->timing_slots) {
-        const size_t e0 = ((size_t)E->timing_runs * P.n_steps + s) * 2;
-        HIPCHECK(hipEventRecord(E->events[e0], E->stream));
-        HIPCHECK(hipEventRecord(E->events[e0 + 1], E->stream));
-      }
-      continue;
-    }
-    if (!E->zl.empty() && E->zl[s].on) {
-      const Exec::ZipLat& L = E->zl[s];
-      const Exec::ZipDesc& zd = L.d;
-      const Step& s1 = P.steps[s - 1];
-      const int S = ZM / L.mp, nub = zd.U / 16;
-      const bool eager = E->eager_rescale;
-      ZipLatArgs z{};
-      z.ptrs = E->d_ptrs; z.n_tensors = E->n_tensors;
-      z.idE = s1.lhs; z.idX = s1.rhs; z.idY = st.rhs;
-      z.slabs_in = (L.from_prev && !eager) ? E->d_zl_slab[L.buf ^ 1] : nullptr;
-      z.slabs_out = E->d_zl_slab[L.buf];
-      z.ldE = zd.ldE; z.ldXq = zd.ldXq; z.ldXk = zd.ldXk; z.ldYq = zd.ldYq; z.ldYm = zd.ldYm;
-      z.U = zd.U; z.R = R;
-      z.partE = nullptr; z.PE = 0; z.strideE = 0; z.numelE = 1.0;
-      if (s1.lhs >= P.n_inputs && P.stabilize && !eager && P.steps[P.tensors[s1.lhs].producer].kernel != CTN_KERNEL_FUSED) {
-        const int ps = P.tensors[s1.lhs].producer;
-        z.partE = E->d_partials + (size_t)E->step_off[ps] * R;
-        z.PE = z.strideE = E->step_partials[ps];
-        z.numelE = (double)P.tensors[s1.lhs].numel;
-      }
-      z.min_norm = P.min_norm;
-      z.partC = E->d_partials + (size_t)E->step_off[s] * R;
-      z.partC_stride = E->step_partials[s];
-      const bool timed_z = E->timing_runs < E->timing_slots;
-      const size_t ez = timed_z ? ((size_t)E->timing_runs * P.n_steps + s) * 2 : 0;
-      if (timed_z) HIPCHECK(hipEventRecord(E->events[ez], E->stream));
-      if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-      E->launched_tile[s] = (L.mp << 16) | ZM;      // (m1 part, all n2) per workgroup, 16 values of u
-      const dim3 gz((unsigned)((int64_t)R * nub * S));
-      z.dbg = nullptr;
-      if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
-        const size_t need = (size_t)gz.x;
-        if (E->dbg_tiles < need) {
-          if (E->d_dbg) (void)hipFree(E->d_dbg);
-          HIPCHECK(hipMalloc((void**)&E->d_dbg, need * 64));
-          E->dbg_tiles = need;
-        }
-        z.dbg = E->d_dbg;
-        HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
-      }
-      if (zd.Q == 4 && L.mp == 32) hipLaunchKernelGGL((k_zip_lat<4, 32>), gz, dim3(512), 0, E->stream, z);
-      else if (zd.Q == 4) hipLaunchKernelGGL((k_zip_lat<4, 64>), gz, dim3(512), 0, E->stream, z);
-      else hipLaunchKernelGGL((k_zip_lat<2, 64>), gz, dim3(512), 0, E->stream, z);
-      if (!L.feeds_next || eager) {                 // nobody adds these slabs up while loading them: do it here
-        hipLaunchKernelGGL(k_zip_slab_sum, dim3((unsigned)E->step_partials[s], (unsigned)R), dim3(256), 0, E->stream,
-                           (const float*)z.slabs_out, S, zd.U, (void* const*)E->d_ptrs, E->n_tensors, st.out, zd.ldC, z.partC,
-                           z.partC_stride);
-        if (eager && P.stabilize && s + 1 < P.n_steps) {
-          const int64_t numel = P.tensors[st.out].numel;
-          const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / 4 + 255) / 256, 2048)), R);
-          hipLaunchKernelGGL(k_renorm<float>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
-                             (const double*)z.partC, E->step_partials[s], E->step_partials[s], P.min_norm);
-        }
-      }
-      if (timed_z) HIPCHECK(hipEventRecord(E->events[ez + 1], E->stream));
-      continue;
-    }
-    if (!E->zip_skip.empty() && E->zip_skip[s]) {   // first step of a zipper pair: runs inside the next step's launch
-      if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-      E->launched_tile[s] = (1 << 16) | 1;          // marker: absorbed into the next launched step
-      if (E->timing_runs < E->timing_slots) {
-        const size_t e0 = ((size_t)E->timing_runs * P.n_steps + s) * 2;
-        HIPCHECK(hipEventRecord(E->events[e0], E->stream));
-        HIPCHECK(hipEventRecord(E->events[e0 + 1], E->stream));
-      }
-      continue;
-    }
-    if (!E->zip.empty() && E->zip[s].on) {
-      const Exec::ZipDesc& zd = E->zip[s];
-      const Step& s1 = P.steps[s - 1];
-      ZipArgs z{};
-      z.ptrs = E->d_ptrs; z.n_tensors = E->n_tensors;
-      z.idE = s1.lhs; z.idX = s1.rhs; z.idY = st.rhs; z.idC = st.out;
-      z.ldE = zd.ldE; z.ldXq = zd.ldXq; z.ldXk = zd.ldXk; z.ldYq = zd.ldYq; z.ldYm = zd.ldYm; z.ldC = zd.ldC;
-      z.K1 = zd.K1; z.Q = zd.Q; z.U = zd.U;
-      z.partE = nullptr; z.PE = 0; z.strideE = 0; z.numelE = 1.0;
-      if (s1.lhs >= P.n_inputs && P.stabilize && !E->eager_rescale && P.steps[P.tensors[s1.lhs].producer].kernel != CTN_KERNEL_FUSED) {
-        const int ps = P.tensors[s1.lhs].producer;
-        z.partE = E->d_partials + (size_t)E->step_off[ps] * R;
-        z.PE = z.strideE = E->step_partials[ps];
-        z.numelE = (double)P.tensors[s1.lhs].numel;
-      }
-      z.min_norm = P.min_norm;
-      z.partC = E->d_partials + (size_t)E->step_off[s] * R;
-      z.partC_stride = E->step_partials[s];
-      z.R = R; z.dbg = nullptr;
-      z.n_items = (int32_t)zipq_items(R, zd.U, zd.zu);
-      const bool timed_z = E->timing_runs < E->timing_slots;
-      const size_t ez = timed_z ? ((size_t)E->timing_runs * P.n_steps + s) * 2 : 0;
-      if (timed_z) HIPCHECK(hipEventRecord(E->events[ez], E->stream));
-      if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-      if ((int)E->launched_form.size() != P.n_steps) E->launched_form.assign(P.n_steps, 0);
-      E->launched_form[s] = zd.f64 ? CTN_FORM_ZIP_F64 : zd.zm == Z4M ? CTN_FORM_ZIPM64 : zd.zm == Z1M ? CTN_FORM_ZIP128
-                            : zd.zu == 64 ? CTN_FORM_ZIP64 : zd.zqp ? CTN_FORM_ZIPQP : zd.zq ? CTN_FORM_ZIPQ : CTN_FORM_ZIP;
-      // the fused pair: 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256):
-      // an fp64 step with 128 tile columns reads as k_mfma_f64_g
-      // k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a wave sums; k_zipm64_f32 (bond 64) likewise
-      // (256, 32): its 256 threads, 32 values of m1 per wave - a tile no plain form reports (theirs are 16 x 16 or have
-      // 64 columns at least)
-      E->launched_tile[s] = zd.zm == Z4M ? ((256 << 16) | 32) : (512 << 16) | (zd.zm == Z1M ? 64 : (zd.zu == 64 && !zd.f64) ? 128 : 256);
-      const int per = zd.U / zd.zu;
-      if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
-        const size_t need = (size_t)per * R;
-        if (E->dbg_tiles < need) {
-          if (E->d_dbg) (void)hipFree(E->d_dbg);
-          HIPCHECK(hipMalloc((void**)&E->d_dbg, need * 64));
-          E->dbg_tiles = need;
-        }
-        z.dbg = E->d_dbg;
-        HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
-      }
-      if (zd.f64) hipLaunchKernelGGL(k_zip_f64, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
-      else if (zd.zm == Z4M) hipLaunchKernelGGL(k_zipm64_f32, dim3((unsigned)((int64_t)per * R)), dim3(256), 0, E->stream, z);
-      else if (zd.zm == Z1M) hipLaunchKernelGGL(k_zip128_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
-      else if (zd.zu == 64) hipLaunchKernelGGL(k_zip64_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
-      else if (zd.zqp) hipLaunchKernelGGL(k_zipqp_f32, dim3((unsigned)zipq_grid(z.n_items, E->n_cu, E->sw.zipq_wgs)), dim3(256), 0, E->stream, z);
-      else if (zd.zq) hipLaunchKernelGGL(k_zipq_f32, dim3((unsigned)((int64_t)per * R)), dim3(256), 0, E->stream, z);
-      else hipLaunchKernelGGL(k_zip_f32, dim3((unsigned)((int64_t)per * R)), dim3(512), 0, E->stream, z);
-      if (E->eager_rescale && P.stabilize && s + 1 < P.n_steps) {
-        const int64_t numel = P.tensors[st.out].numel;
-        const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / (zd.f64 ? 2 : 4) + 255) / 256, 2048)), R);
-        if (zd.f64)
-          hipLaunchKernelGGL(k_renorm<double>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
-                             (const double*)z.partC, E->step_partials[s], E->step_partials[s], P.min_norm);
-        else
-          hipLaunchKernelGGL(k_renorm<float>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
-                             (const double*)z.partC, E->step_partials[s], E->step_partials[s], P.min_norm);
-      }
-      if (timed_z) HIPCHECK(hipEventRecord(E->events[ez + 1], E->stream));
-      continue;
-    }
-    if (!E->cplx_skip.empty() && E->cplx_skip[s]) {   // the S step of a complex pair: runs inside the next step's launch
-      if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-      E->launched_tile[s] = (1 << 16) | 1;          // marker: absorbed into the next launched step
-      if (E->timing_runs < E->timing_slots) {
-        const size_t e0 = ((size_t)E->timing_runs * P.n_steps + s) * 2;
-        HIPCHECK(hipEventRecord(E->events[e0], E->stream));
-        HIPCHECK(hipEventRecord(E->events[e0 + 1], E->stream));
-      }
-      continue;
-    }
-    if (st.kernel == CTN_KERNEL_FUSED) {   // formed on the fly inside its consumer: nothing to launch
-      if (E->timing_runs < E->timing_slots) {
-        const size_t e0 = ((size_t)E->timing_runs * P.n_steps + s) * 2;
-        HIPCHECK(hipEventRecord(E->events[e0], E->stream));
-        HIPCHECK(hipEventRecord(E->events[e0 + 1], E->stream));
-      }
-      continue;
-    }
-    StepArgs a;
-    const int32_t* T = E->d_tables;
-    const int64_t* T8 = E->d_tables64;
-    a.obA = T8 + st.t.obA; a.obB = T8 + st.t.obB; a.obC = T8 + st.t.obC;
-    a.omA = T + st.t.omA; a.omC = T + st.t.omC;
-    a.onB = T + st.t.onB; a.onC = T + st.t.onC;
-    a.okA = T + st.t.okA; a.okB = T + st.t.okB;
-    a.ptrs = E->d_ptrs;
-    auto part_of = [&](int id, const double** p, int32_t* cnt, int32_t* stride, double* numel) {
-      *p = nullptr; *cnt = 0; *stride = 0; *numel = 1;
-      if (id >= P.n_inputs && P.stabilize && !E->eager_rescale && P.steps[P.tensors[id].producer].kernel != CTN_KERNEL_FUSED) {
-        const int ps = P.tensors[id].producer;
-        *p = E->d_partials + (size_t)E->step_off[ps] * R;
-        *cnt = *stride = E->step_partials[ps];
-        *numel = (double)P.tensors[id].numel;
-      }
-    };
-    part_of(st.lhs, &a.partA, &a.PA, &a.strideA, &a.numelA);
-    part_of(st.rhs, &a.partB, &a.PB, &a.strideB, &a.numelB);
-    part_of(st.lhs2, &a.partA2, &a.PA2, &a.strideA2, &a.numelA2);
-    a.obA2 = T8 + st.t.obA2; a.omA2 = T + st.t.omA2; a.okA2 = T + st.t.okA2;
-    a.idA2 = st.lhs2 >= 0 ? st.lhs2 : E->n_tensors - 1;
-    a.krX = st.krX; a.krY = st.krY;
-    a.epw = st.epw | (st.epw_split ? 0x100 : 0);
-    double* part_dst = E->d_partials + (size_t)E->step_off[s] * R;
-    const int part_stride = E->step_partials[s];    // slots per replica of this step's region
-    a.partC = st.collapse ? E->d_scratch : part_dst;
-    a.partC_stride = st.collapse ? st.blocks : part_stride;
-    int collapse_blocks = st.blocks;   // partials written per replica when the step collapses (a launcher may retile)
-    bool reduced = false;              // a K-split streaming / row-dot step: its reduce pass wrote the partials itself
-    bool do_collapse = st.collapse;    // more workgroup partials than slots: through the scratch buffer and k_collapse
-    a.min_norm = P.min_norm;
-    a.Bt = (int32_t)st.Bt; a.M = (int32_t)st.M; a.N = (int32_t)st.N; a.K = (int32_t)st.K;
-    a.idA = st.lhs; a.idB = st.rhs >= 0 ? st.rhs : E->n_tensors - 1; a.idC = st.out;
-    a.n_tensors = E->n_tensors;
-    const int row_tile = (st.kernel == CTN_KERNEL_MFMA_F32 && st.tileM == 64) ? 64 : kTileM;
-    a.tiles_m = (int32_t)((st.M + row_tile - 1) / row_tile);
-    a.tiles_n = (int32_t)((st.N + kTileN - 1) / kTileN);
-    a.blocks_per_replica = st.blocks;
-    a.R = R;
-    a.c_vec = (st.cvec && (s + 1 < P.n_steps || E->outs_aligned16)) ? 1 : 0;
-    a.dbg = nullptr;
-    a.ks_slab = nullptr; a.ks_numelC = 0; a.ks_S = 0; a.ks_chunk = 0;
-    a.ohA = T8 + st.t.ohA; a.ohB = T8 + st.t.ohB; a.ohC = T8 + st.t.ohC;
-    a.olA = T + st.t.olA; a.olB = T + st.t.olB; a.olC = T + st.t.olC;
-    a.H = (int32_t)st.H; a.L = (int32_t)st.L; a.Nv = (int32_t)st.Nv;
-    a.sAn = (int32_t)st.sAn; a.sBn = (int32_t)st.sBn;
-    a.dNq = make_fastdiv((st.Nv + st.vecw - 1) / st.vecw);
-    a.dL = make_fastdiv(st.L);
-    a.dNv = make_fastdiv(st.Nv);
+  const StepTimer t(E, 0);
+  if (t.rc != CTN_OK) return t.rc;
+  if (E->d_chain_prog && P.dtype == CTN_F32)
+    hipLaunchKernelGGL(k_chain_lds<float>, dim3(R), dim3(256), 0, E->stream, (const int32_t*)E->d_chain_prog, E->chain_len0, P.n_steps,
+                       (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
+  else if (E->d_chain_prog)
+    hipLaunchKernelGGL(k_chain_lds<double>, dim3(R), dim3(256), 0, E->stream, (const int32_t*)E->d_chain_prog, E->chain_len0, P.n_steps,
+                       (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
+  else if (P.dtype == CTN_F32)
+    hipLaunchKernelGGL(k_chain<float>, dim3(R), dim3(256), 0, E->stream, (const ChainStep*)E->d_chain, P.n_steps,
+                       (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
+  else
+    hipLaunchKernelGGL(k_chain<double>, dim3(R), dim3(256), 0, E->stream, (const ChainStep*)E->d_chain, P.n_steps,
+                       (void* const*)E->d_ptrs, E->n_tensors, E->d_partials, R, P.min_norm, P.stabilize ? 1 : 0);
+  return t.end();
+}
 
-    const bool timed = E->timing_runs < E->timing_slots;  // only the first `slots` enqueues are bracketed
-    const size_t ev0 = timed ? ((size_t)E->timing_runs * P.n_steps + s) * 2 : 0;
-    if (timed) HIPCHECK(hipEventRecord(E->events[ev0], E->stream));
-    if ((int)E->launched_tile.size() != P.n_steps) E->launched_tile.assign(P.n_steps, 0);
-    auto used_tile = [&](int tm, int tn) { E->launched_tile[s] = (tm << 16) | tn; };
-    switch (st.kernel) {
-      case CTN_KERNEL_MFMA_F32: {
-        const int64_t total = (int64_t)st.blocks * R;
-        if (total >= (1LL << 31)) { g_err = "grid too large"; return CTN_UNSUPPORTED; }
-        if (!E->cplx.empty() && E->cplx[s].on) {
-          // a complex x complex step: the S step before it and this GEMM as one launch (k_cmfma_f32), reading `small`
-          // and `big` as arrays of pairs; the scales are those of `small` (not of the never-written mid) and of `big`
-          const CplxDesc& cd = E->cplx[s];
-          const int32_t* CT = E->d_cplx_tabs;
-          CplxArgs c{};
-          c.txr = CT + cd.txr; c.txk = CT + cd.txk; c.tyn = CT + cd.tyn; c.tyk = CT + cd.tyk; c.tcx = CT + cd.tcx; c.tcy = CT + cd.tcy;
-          c.ptrs = E->d_ptrs;
-          part_of(cd.small, &c.partX, &c.PX, &c.strideX, &c.numelX);
-          part_of(cd.big, &c.partY, &c.PY, &c.strideY, &c.numelY);
-          c.min_norm = P.min_norm;
-          c.Mx = cd.Mx; c.Ny = cd.Ny; c.Kc = cd.Kc;
-          c.idX = cd.small; c.idY = cd.big; c.idS = cd.sid; c.idC = st.out; c.n_tensors = E->n_tensors;
-          c.tiles_x = (cd.Mx + CX_TX - 1) / CX_TX; c.tiles_y = (cd.Ny + CX_TY - 1) / CX_TY;
-          c.blocks_per_replica = c.tiles_x * c.tiles_y; c.R = R;
-          c.sa = cd.sa; c.sb = cd.sb; c.so = cd.so; c.sO = cd.sO; c.legx = cd.legx; c.legy = cd.legy;
-          c.c_vec2 = (cd.cvec2 && (s + 1 < P.n_steps || E->outs_aligned16)) ? 1 : 0;
-          if (c.blocks_per_replica > kMaxPartials) {       // more workgroups than slots: through the collapse pass
-            do_collapse = true; collapse_blocks = c.blocks_per_replica;
-            c.partC = E->d_scratch; c.partC_stride = collapse_blocks;
-          } else {
-            do_collapse = false;
-            c.partC = part_dst; c.partC_stride = part_stride;
-          }
-          used_tile(CX_TX, 2 * CX_TY);   // 64 pairs of `small` x (128 entries of `big` x 2 components): no plain form reports it
-          const dim3 gc((unsigned)((int64_t)c.blocks_per_replica * R));
-          if (cd.kfx && cd.kfy) hipLaunchKernelGGL((k_cmfma_f32<true, true>), gc, dim3(256), 0, E->stream, c);
-          else if (cd.kfx) hipLaunchKernelGGL((k_cmfma_f32<true, false>), gc, dim3(256), 0, E->stream, c);
-          else if (cd.kfy) hipLaunchKernelGGL((k_cmfma_f32<false, true>), gc, dim3(256), 0, E->stream, c);
-          else hipLaunchKernelGGL((k_cmfma_f32<false, false>), gc, dim3(256), 0, E->stream, c);
-          break;
-        }
-        if (const int ntw_av = (int)E->ares_ntw.size() == P.n_steps ? E->ares_ntw[s] : 0) {
-          const int ntw = ntw_av & 0xffff, avec = ntw_av >> 16;
-          // the left operand resident in registers, `ntw` column tiles per workgroup (k_mfma_f32_ares); one partial per
-          // workgroup through the collapse pass the step has anyway
-          const int wgs = (int)(st.Bt * (st.N / AR_TN / ntw));
-          a.partC = E->d_scratch; a.partC_stride = wgs;
-          do_collapse = true; collapse_blocks = wgs;
-          used_tile(256, std::min(AR_TN * ntw, 32768));
-          const dim3 ga((unsigned)((int64_t)wgs * R));
-          if (st.modeB == 2) {
-            if (avec) hipLaunchKernelGGL((k_mfma_f32_ares<2, 1>), ga, dim3(512), 0, E->stream, a, ntw);
-            else hipLaunchKernelGGL((k_mfma_f32_ares<2, 0>), ga, dim3(512), 0, E->stream, a, ntw);
-          } else {
-            if (avec) hipLaunchKernelGGL((k_mfma_f32_ares<1, 1>), ga, dim3(512), 0, E->stream, a, ntw);
-            else hipLaunchKernelGGL((k_mfma_f32_ares<1, 0>), ga, dim3(512), 0, E->stream, a, ntw);
-          }
-          break;
-        }
-        if (const int S = (E->d_slab && s + 1 < P.n_steps) ? g_splitk(st, R, E->n_cu, E->mfma_g, E->sw, st.cvec) : 0) {
-          SplitKArgs sk{};
-          sk.slab = E->d_slab;
-          sk.numelC = P.tensors[st.out].numel;
-          sk.S = S;
-          sk.kchunk = (int32_t)(st.K / S);
-          a.ks_slab = sk.slab; a.ks_numelC = sk.numelC; a.ks_S = S; a.ks_chunk = sk.kchunk;
-          a.tiles_m = (int32_t)((st.M + GM - 1) / GM);
-          a.tiles_n = (int32_t)((st.N + st.tileN - 1) / st.tileN);
-          a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n * S);
-          used_tile(256, 128);
-          const dim3 gg((unsigned)((int64_t)a.blocks_per_replica * R));
-          const bool use_asm = !E->sw.g_no_asm;          // (every split is whole k-tiles)
-#define CTN_G_LAUNCH(AA, BB)                                                                             \
-          do {                                                                                           \
-            if (use_asm) hipLaunchKernelGGL((k_mfma_f32_g<4, 2, true, AA, BB>), gg, dim3(256), 0, E->stream, a); \
-            else hipLaunchKernelGGL((k_mfma_f32_g<4, 2, false, AA, BB>), gg, dim3(256), 0, E->stream, a);        \
-          } while (0)
-          if (st.modeA == 2 && st.modeB == 1) CTN_G_LAUNCH(2, 1);
-          else if (st.modeA == 1 && st.modeB == 2) CTN_G_LAUNCH(1, 2);
-          else if (st.modeA == 2 || st.modeB == 2) CTN_G_LAUNCH(2, 2);
-          else CTN_G_LAUNCH(1, 1);
-#undef CTN_G_LAUNCH
-          a.ks_slab = nullptr; a.ks_S = 0;
-          a.partC = part_dst; a.partC_stride = part_stride; reduced = true;
-          launch_splitk_reduce<float>(E, E->step_partials[s], R, a, sk);
-          break;
-        }
-        if (const int T = lat_form(st, R, E->n_cu, P.dtype, E->sw)) {
-          a.tiles_m = (int32_t)((st.M + T - 1) / T);
-          a.tiles_n = (int32_t)((st.N + T - 1) / T);
-          a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n);
-          a.partC = part_dst; a.partC_stride = part_stride; reduced = true;   // one partial per tile, written directly
-          const int ks = T == 64 ? 2 : 8, kp = T == 16 ? 4 : 2;
-          const int kchunk = (int)(((st.K + ks - 1) / ks + kp - 1) / kp * kp);
-          used_tile(T, T);
-          const dim3 g((unsigned)((int64_t)a.blocks_per_replica * R));
-          if (T == 16) hipLaunchKernelGGL((k_mfma_lat<16, float>), g, dim3(512), 0, E->stream, a, kchunk);
-          else if (T == 32) hipLaunchKernelGGL((k_mfma_lat<32, float>), g, dim3(512), 0, E->stream, a, kchunk);
-          else hipLaunchKernelGGL((k_mfma_lat<64, float>), g, dim3(512), 0, E->stream, a, kchunk);
-          break;
-        }
-        if (const int S = E->d_slab ? splitk_splits(st, R, E->n_cu, P.dtype, E->sw) : 0) {
-          SplitKArgs sk;
-          sk.slab = E->d_slab;
-          sk.numelC = P.tensors[st.out].numel;
-          sk.S = S;
-          sk.kchunk = (int32_t)(((st.K + S - 1) / S + 31) / 32 * 32);
-          sk.S = (int32_t)((st.K + sk.kchunk - 1) / sk.kchunk);  // drop empty trailing splits
-          sk.tiles_m = (int32_t)((st.M + 63) / 64);
-          sk.tiles_n = (int32_t)((st.N + 63) / 64);
-          sk.tiles_per_replica = (int32_t)(st.Bt * sk.tiles_m * sk.tiles_n);
-          used_tile(64, 64);
-          launch_sk(st.modeA, st.modeB, dim3((unsigned)((int64_t)sk.tiles_per_replica * sk.S * R)), E->stream, a, sk);
-          launch_splitk_reduce<float>(E, E->step_partials[s], R, a, sk);
-          break;
-        }
-        if (!g_launch(st, R, E->n_cu, E->mfma_g) && s + 1 < P.n_steps && h_form(P, st, R, E->n_cu, P.dtype, E->sw, a.c_vec != 0)) {
-          a.tiles_m = (int32_t)((st.M + 127) / 128);
-          a.tiles_n = (int32_t)((st.N + 127) / 128);
-          a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n);
-          a.partC = part_dst; a.partC_stride = part_stride; do_collapse = false;   // one partial per tile (<= kMaxPartials)
-          if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
-            const size_t need = (size_t)a.blocks_per_replica * R;
-            if (E->dbg_tiles < need) {
-              if (E->d_dbg) (void)hipFree(E->d_dbg);
-              HIPCHECK(hipMalloc((void**)&E->d_dbg, need * 64));
-              E->dbg_tiles = need;
-            }
-            a.dbg = E->d_dbg;
-            HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
-          }
-          used_tile(128, 128);
-          const dim3 gh((unsigned)((int64_t)a.blocks_per_replica * R));
-#define CTN_H_LAUNCH(AA, BB)                                                                              \
-          do {                                                                                            \
-            if (st.epw == 4) hipLaunchKernelGGL((k_mfma_f32_h<AA, BB, 4>), gh, dim3(512), 0, E->stream, a);      \
-            else if (st.epw == 2) hipLaunchKernelGGL((k_mfma_f32_h<AA, BB, 2>), gh, dim3(512), 0, E->stream, a); \
-            else hipLaunchKernelGGL((k_mfma_f32_h<AA, BB, 0>), gh, dim3(512), 0, E->stream, a);                  \
-          } while (0)
-          if (st.modeA == 2 && st.modeB == 2) CTN_H_LAUNCH(2, 2);
-          else if (st.modeA == 2) CTN_H_LAUNCH(2, 1);
-          else if (st.modeB == 2) CTN_H_LAUNCH(1, 2);
-          else CTN_H_LAUNCH(1, 1);
-#undef CTN_H_LAUNCH
-          break;
-        }
-        a.tiles_n = (int32_t)((st.N + st.tileN - 1) / st.tileN);
-        if (E->sw.stamps && (E->sw.stamp_step < 0 || E->sw.stamp_step == s)) {
-          if (E->dbg_tiles < (size_t)total) {
-            if (E->d_dbg) (void)hipFree(E->d_dbg);
-            HIPCHECK(hipMalloc((void**)&E->d_dbg, (size_t)total * 64));
-            E->dbg_tiles = (size_t)total;
-          }
-          a.dbg = E->d_dbg;
-          HIPCHECK(hipMemsetAsync(E->d_dbg, 0, E->dbg_tiles * 64, E->stream));
-        }
-        // large-tile LDS-DMA variant (kernels_mfma_g.h) where the step's shape allows it.
-        // CTN_MFMA_G (read when the executor is created): 0 = never, 1 = 256x128 tiles when the launch
-        // fills the chip (default), 2 = whenever eligible (tests)
-        const int use_g = E->mfma_g;
-        static_assert(GM == 256 && GN == kTileN && GK == 16 && 2 * GK == 32, "planner eligibility rule (plan.cpp) assumes these");
-        // ... and the launch has at least two of the big tiles per CU: with fewer, 128-row tiles spread the
-        // same work over more CUs (measured: 2048^3 runs at 90 vs 56 TFLOP/s, 4096^3 at 125 vs 135)
-        const int64_t gtiles = st.Bt * ((st.M + GM - 1) / GM) * a.tiles_n * R;
-        const bool no_asm = E->sw.g_no_asm;
-        const bool kcontig = st.modeA == 2 || st.modeB == 2;
-        // ... and K >= 192: below that the 128-tile kernel's 3-4 workgroups per CU hide the per-tile cost
-        // better (8192 x 8192 x K: K = 64 old +7 %, 128 +2 %, 192 equal, 256 large tiles +5 %)
-        // ... and long K (>= 1024) already from 3/4 of a tile per CU: the per-tile cost amortises over the k loop
-        // (256 x 256 x 1024 per replica, R = 96 / 128: 86.9 / 106.2 vs 80.3 / 95.8 TFLOP/s; R = 48 / 64 lose)
-        if (g_launch(st, R, E->n_cu, use_g) && a.c_vec) {
-          a.tiles_m = (int32_t)((st.M + GM - 1) / GM);
-          // long-K steps on narrow outputs whose tiles are all full also exist as 256 x 256 tiles (8 waves, one
-          // workgroup per CU): with N <= 512 each A tile is fetched half as often (256 x 256 x 1024 per replica:
-          // 133.9 vs 130.3 TFLOP/s); K = 256 steps (116.0 vs 116.7) and wide outputs (8192 x 8192 x 768: 130.3 vs
-          // 132.1) are better off with 256 x 128
-          // - and so are very long K on any width (K = 2048 ... 8192: +1.5 ... +3 %)
-          const bool big = use_g == 1 && E->sw.g_big && !kcontig && st.M % 256 == 0 && st.N % 256 == 0 && st.K % GK == 0 &&
-                           ((st.K >= 512 && st.N <= 512) || st.K >= E->sw.g_big_min_k) && gtiles / 2 >= (int64_t)E->n_cu;
-          if (big) {
-            used_tile(256, 256);
-            a.tiles_n = (int32_t)(st.N / 256);
-            a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n);
-            hipLaunchKernelGGL((k_mfma_f32_g<8, 2, true>), dim3((unsigned)((int64_t)a.blocks_per_replica * R)), dim3(512), 0,
-                               E->stream, a);
-            break;
-          }
-          {
-            used_tile(256, 128);
-            a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n);
-            const dim3 gg((unsigned)((int64_t)a.blocks_per_replica * R));
-            // hand-scheduled blocks for whole k-tiles, the C++ loop (which masks a ragged last k-tile) otherwise
-            const bool use_asm = st.K % GK == 0 && !no_asm;
-#define CTN_G_LAUNCH(AA, BB)                                                                             \
-            do {                                                                                         \
-              if (use_asm) hipLaunchKernelGGL((k_mfma_f32_g<4, 2, true, AA, BB>), gg, dim3(256), 0, E->stream, a); \
-              else hipLaunchKernelGGL((k_mfma_f32_g<4, 2, false, AA, BB>), gg, dim3(256), 0, E->stream, a);        \
-            } while (0)
-            if (st.modeA == 2 && st.modeB == 1) CTN_G_LAUNCH(2, 1);
-            else if (st.modeA == 1 && st.modeB == 2) CTN_G_LAUNCH(1, 2);
-            else if (kcontig) CTN_G_LAUNCH(2, 2);
-            else CTN_G_LAUNCH(1, 1);
-#undef CTN_G_LAUNCH
-          }
-          break;
-        }
-        // register-staged tiles; halved (128 -> 64 rows / columns) while the launch is under-filled - see plain_tiles
-        int tm = row_tile, tn = st.tileN;
-        plain_tiles(st, R, E->n_cu, E->mfma_g, s + 1 == P.n_steps, &tm, &tn, E->sw.halve);
-        a.tiles_m = (int32_t)((st.M + tm - 1) / tm);
-        a.tiles_n = (int32_t)((st.N + tn - 1) / tn);
-        a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n);
-        if (a.blocks_per_replica > kMaxPartials) {             // (halved tiles may exceed the slots: collapse them)
-          do_collapse = true;
-          collapse_blocks = a.blocks_per_replica;
-          a.partC = E->d_scratch;
-          a.partC_stride = collapse_blocks;
-        } else {
-          a.partC_stride = part_stride;                        // == blocks_per_replica (ctn_exec_create used the same rule)
-        }
-        used_tile(tm, tn);
-        launch_mfma(st.modeA, st.modeB, tm, tn, dim3((unsigned)((int64_t)a.blocks_per_replica * R)), E->stream, a, E->sw);
-        break;
-      }
-      case CTN_KERNEL_MFMA_F64: {
-        const int64_t total = (int64_t)st.blocks * R;
-        if (total >= (1LL << 31)) { g_err = "grid too large"; return CTN_UNSUPPORTED; }
-        if (const int T = lat_form(st, R, E->n_cu, P.dtype, E->sw)) {      // one-launch latency form, 16 x 16 tiles
-          a.tiles_m = (int32_t)((st.M + T - 1) / T);
-          a.tiles_n = (int32_t)((st.N + T - 1) / T);
-          a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n);
-          a.partC = part_dst; a.partC_stride = part_stride; reduced = true;
-          const int kchunk = (int)(((st.K + 7) / 8 + 3) / 4 * 4);
-          used_tile(T, T);
-          hipLaunchKernelGGL((k_mfma_lat<16, double>), dim3((unsigned)((int64_t)a.blocks_per_replica * R)), dim3(512), 0,
-                             E->stream, a, kchunk);
-          break;
-        }
-        if (const int S = E->d_slab ? splitk_splits(st, R, E->n_cu, P.dtype, E->sw) : 0) {   // latency mode, as in fp32
-          SplitKArgs sk;
-          sk.slab = E->d_slab;
-          sk.numelC = P.tensors[st.out].numel;
-          sk.kchunk = (int32_t)(((st.K + S - 1) / S + 31) / 32 * 32);
-          sk.S = (int32_t)((st.K + sk.kchunk - 1) / sk.kchunk);  // drop empty trailing splits
-          sk.tiles_m = (int32_t)((st.M + 63) / 64);
-          sk.tiles_n = (int32_t)((st.N + 63) / 64);
-          sk.tiles_per_replica = (int32_t)(st.Bt * sk.tiles_m * sk.tiles_n);
-          used_tile(64, 64);
-          launch_sk64(st.modeA, st.modeB, dim3((unsigned)((int64_t)sk.tiles_per_replica * sk.S * R)), E->stream, a, sk);
-          launch_splitk_reduce<double>(E, E->step_partials[s], R, a, sk);
-          break;
-        }
-        a.tiles_m = (int32_t)((st.M + kTile64M - 1) / kTile64M);
-        if (E->mfma_g && st.tileN == DN) {  // 128 x 128 LDS-DMA kernel, under the same launch-size rule as fp32
-          const int64_t gtiles = st.Bt * a.tiles_m * ((st.N + DN - 1) / DN) * R;
-          if (E->mfma_g >= 2 || gtiles >= 2LL * E->n_cu) {
-            used_tile(128, 128);
-            a.tiles_n = (int32_t)((st.N + DN - 1) / DN);
-            a.blocks_per_replica = (int32_t)(st.Bt * a.tiles_m * a.tiles_n);
-            const dim3 gg((unsigned)gtiles);
-            if (st.modeA == 2 && st.modeB == 2) hipLaunchKernelGGL((k_mfma_f64_g<2, 2>), gg, dim3(256), 0, E->stream, a);
-            else if (st.modeA == 2) hipLaunchKernelGGL((k_mfma_f64_g<2, 1>), gg, dim3(256), 0, E->stream, a);
-            else if (st.modeB == 2) hipLaunchKernelGGL((k_mfma_f64_g<1, 2>), gg, dim3(256), 0, E->stream, a);
-            else hipLaunchKernelGGL((k_mfma_f64_g<1, 1>), gg, dim3(256), 0, E->stream, a);
-            break;
-          }
-        }
-        used_tile(128, 64);
-        a.tiles_n = (int32_t)((st.N + kTile64N - 1) / kTile64N);
-        const dim3 g((unsigned)total), b(256);
-#define CTN_F64(AA, BB) hipLaunchKernelGGL((k_mfma_f64<AA, BB>), g, b, 0, E->stream, a)
-        switch (st.modeA * 3 + st.modeB) {
-          case 0: CTN_F64(0, 0); break; case 1: CTN_F64(0, 1); break; case 2: CTN_F64(0, 2); break;
-          case 3: CTN_F64(1, 0); break; case 4: CTN_F64(1, 1); break; case 5: CTN_F64(1, 2); break;
-          case 6: CTN_F64(2, 0); break; case 7: CTN_F64(2, 1); break; default: CTN_F64(2, 2); break;
-        }
-#undef CTN_F64
-        break;
-      }
-      case CTN_KERNEL_DOT:
-        if (const int S0 = E->d_slab ? dot_splits(st) : 0) {
-          SplitKArgs sk{};
-          sk.slab = E->d_slab;
-          sk.numelC = P.tensors[st.out].numel;
-          sk.kchunk = (int32_t)(((st.K + S0 - 1) / S0 + 255) / 256 * 256);
-          sk.S = (int32_t)((st.K + sk.kchunk - 1) / sk.kchunk);
-          const dim3 g((unsigned)((int64_t)st.blocks * sk.S), R);
-          const Exec::DotTr dt = (int)E->dot_tr.size() == P.n_steps ? E->dot_tr[s] : Exec::DotTr();
-          if (P.dtype == CTN_F32) {
-            if (dt.on) hipLaunchKernelGGL(k_dot_tr<float>, g, dim3(256), 0, E->stream, a, (float*)sk.slab, sk.numelC, sk.S, dt.Ka, dt.Kb, dt.ldY, dt.x_is_a);
-            else hipLaunchKernelGGL(k_dot_split<float>, g, dim3(256), 0, E->stream, a, (float*)sk.slab, sk.numelC, sk.S, sk.kchunk);
-            launch_splitk_reduce<float>(E, E->step_partials[s], R, a, sk);
-          } else {
-            if (dt.on) hipLaunchKernelGGL(k_dot_tr<double>, g, dim3(256), 0, E->stream, a, (double*)sk.slab, sk.numelC, sk.S, dt.Ka, dt.Kb, dt.ldY, dt.x_is_a);
-            else hipLaunchKernelGGL(k_dot_split<double>, g, dim3(256), 0, E->stream, a, (double*)sk.slab, sk.numelC, sk.S, sk.kchunk);
-            launch_splitk_reduce<double>(E, E->step_partials[s], R, a, sk);
-          }
-          break;
-        }
-        if (P.dtype == CTN_F32) hipLaunchKernelGGL(k_dot<float>, dim3(st.blocks, R), dim3(256), 0, E->stream, a);
-        else hipLaunchKernelGGL(k_dot<double>, dim3(st.blocks, R), dim3(256), 0, E->stream, a);
-        break;
-      case CTN_KERNEL_ROWDOT: {
-        const int ks = E->d_slab ? rowdot_splits(st, R, E->n_cu) : 0;
-        SplitKArgs sk{};
-        if (ks) {
-          sk.slab = E->d_slab;
-          sk.numelC = P.tensors[st.out].numel;
-          sk.kchunk = (int32_t)(((st.K + ks - 1) / ks + 63) / 64 * 64);
-          sk.S = (int32_t)((st.K + sk.kchunk - 1) / sk.kchunk);
-          a.ks_slab = sk.slab; a.ks_numelC = sk.numelC; a.ks_S = sk.S; a.ks_chunk = sk.kchunk;
-        }
-        const dim3 g(st.blocks, R, ks ? sk.S : 1);
-        if (P.dtype == CTN_F32) hipLaunchKernelGGL(k_rowdot<float>, g, dim3(256), 0, E->stream, a);
-        else hipLaunchKernelGGL(k_rowdot<double>, g, dim3(256), 0, E->stream, a);
-        if (ks) {
-          a.partC = part_dst; a.partC_stride = part_stride; reduced = true;
-          if (P.dtype == CTN_F32) launch_splitk_reduce<float>(E, E->step_partials[s], R, a, sk);
-          else launch_splitk_reduce<double>(E, E->step_partials[s], R, a, sk);
-        }
-        break;
-      }
-      default: {
-        if (st.kvec) {   // short unit-stride K of the left operand: one output per thread, 16-byte loads along k
-          a.dNv = make_fastdiv(st.Nv);
-          if (P.dtype == CTN_F32) hipLaunchKernelGGL(k_stream_kvec<float>, dim3(st.blocks, R), dim3(256), 0, E->stream, a);
-          else hipLaunchKernelGGL(k_stream_kvec<double>, dim3(st.blocks, R), dim3(256), 0, E->stream, a);
-          break;
-        }
-        // vector stores need a 16-byte aligned destination: the caller's final buffer may not be
-        const int vw = (s + 1 == P.n_steps && !E->outs_aligned16) ? 1 : st.vecw;
-        int u;
-        int64_t nq;
-        stream_variant(st, R, vw, &u, &nq);
-        a.dNq = make_fastdiv(nq / u);
-        if (collect_left > 0) {   // a grouped leaf step: keep the arguments; the last one uploads and launches the group
-          Exec::LeafGroup& G = E->groups[collect_head];
-          E->h_group_args[G.off + (s - collect_head)] = a;
-          if (--collect_left == 0) {
-            HIPCHECK(hipMemcpyAsync(E->d_group_args + G.off, E->h_group_args + G.off, sizeof(StepArgs) * G.len,
-                                    hipMemcpyHostToDevice, E->stream));
-            G.ready = true;
-            const dim3 gg(G.blocks, R, G.len);
-            if (P.dtype == CTN_F32) launch_stream_group<float>(G.vw, G.u, gg, E->stream, E->d_group_args + G.off);
-            else launch_stream_group<double>(G.vw, G.u, gg, E->stream, E->d_group_args + G.off);
-          }
-          break;
-        }
-        const int ks = E->d_slab ? stream_splits(st, R, E->n_cu) : 0;
-        SplitKArgs sk{};
-        if (ks) {
-          sk.slab = E->d_slab;
-          sk.numelC = P.tensors[st.out].numel;
-          sk.kchunk = (int32_t)((st.K + ks - 1) / ks);
-          sk.S = (int32_t)((st.K + sk.kchunk - 1) / sk.kchunk);
-          a.ks_slab = sk.slab; a.ks_numelC = sk.numelC; a.ks_S = sk.S; a.ks_chunk = sk.kchunk;
-        }
-        const dim3 g(st.blocks, R, ks ? sk.S : 1), b(256);
-#define CTN_STREAM(TT, VV, UU) hipLaunchKernelGGL((k_stream<TT, VV, UU>), g, b, 0, E->stream, a)
-        if (P.dtype == CTN_F32) {
-          if (vw == 4) { if (u == 4) CTN_STREAM(float, 4, 4); else CTN_STREAM(float, 4, 1); }
-          else { if (u == 4) CTN_STREAM(float, 1, 4); else CTN_STREAM(float, 1, 1); }
-        } else {
-          if (vw == 2) { if (u == 4) CTN_STREAM(double, 2, 4); else CTN_STREAM(double, 2, 1); }
-          else { if (u == 4) CTN_STREAM(double, 1, 4); else CTN_STREAM(double, 1, 1); }
-        }
-#undef CTN_STREAM
-        if (ks) {
-          a.partC = part_dst; a.partC_stride = part_stride; reduced = true;
-          if (P.dtype == CTN_F32) launch_splitk_reduce<float>(E, E->step_partials[s], R, a, sk);
-          else launch_splitk_reduce<double>(E, E->step_partials[s], R, a, sk);
-        }
-        break;
-      }
-    }
-    if (do_collapse && !reduced)
-      hipLaunchKernelGGL(k_collapse, dim3(R), dim3(256), 0, E->stream, (const double*)E->d_scratch, collapse_blocks, part_dst);
-    if (E->eager_rescale && P.stabilize && s + 1 < P.n_steps) {   // the final tensor is normalised by k_finalize
-      const int64_t numel = P.tensors[st.out].numel;
-      const int V = P.dtype == CTN_F64 ? 2 : 4;
-      const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / V + 255) / 256, 2048)), R);
-      if (P.dtype == CTN_F32)
-        hipLaunchKernelGGL(k_renorm<float>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
-                           (const double*)part_dst, E->step_partials[s], part_stride, P.min_norm);
-      else
-        hipLaunchKernelGGL(k_renorm<double>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, st.out, numel,
-                           (const double*)part_dst, E->step_partials[s], part_stride, P.min_norm);
-    }
-    if (timed) HIPCHECK(hipEventRecord(E->events[ev0 + 1], E->stream));
+// a group of leaf steps whose arguments are in device memory
+static void launch_group(Exec* E, const Exec::LeafGroup& G) {
+  const dim3 g(G.blocks, E->R, G.len);
+  if (E->plan->dtype == CTN_F32) launch_stream_group<float>(G.vw, G.u, g, E->stream, E->d_group_args + G.off);
+  else launch_stream_group<double>(G.vw, G.u, g, E->stream, E->d_group_args + G.off);
+}
+
+// the last member of a float64 sweep: 2 S member steps, S sites
+static int launch_sweep64(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const Exec::SweepDesc& sd = E->sweep;
+  const int S = (int)sd.steps.size() / 2;
+  Sweep64Args w{};
+  w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
+  w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M;
+  w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
+  producer_partials(E, sd.idIn, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
+  w.min_norm = P.min_norm;
+  w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
+  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns of C per workgroup, every site
+  {
+    const dim3 gs((unsigned)sd.J, (unsigned)R);
+#define CTN_SWEEP64_LAUNCH(DD)                                                                                        \
+    do {                                                                                                              \
+      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_f64<DD, 4>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);      \
+      else hipLaunchKernelGGL((k_sweep_f64<DD, 2>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);                 \
+    } while (0)
+    if (sd.D == 64) CTN_SWEEP64_LAUNCH(64);
+    else if (sd.D == 128) CTN_SWEEP64_LAUNCH(128);
+    else if (sd.D == 256) CTN_SWEEP64_LAUNCH(256);
+    else CTN_SWEEP64_LAUNCH(512);
+#undef CTN_SWEEP64_LAUNCH
   }
+  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
+  hipLaunchKernelGGL(k_sweep64_z, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
+                     (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
+  Sweep64Finish f{};
+  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
+  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
+  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
+  hipLaunchKernelGGL(k_sweep64_finish, dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+  return CTN_OK;
+}
+
+// the last member of a sweep: the whole chain, then its scale bookkeeping
+static int launch_sweep(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const Exec::SweepDesc& sd = E->sweep;
+  const int S = (int)sd.steps.size();
+  const Step& f0 = P.steps[sd.steps.front()];
+  SweepArgs w{};
+  w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
+  w.idIn = f0.lhs; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M;
+  w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
+  producer_partials(E, f0.lhs, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
+  w.min_norm = P.min_norm;
+  w.rec_a = E->d_sweep_a; w.rec_s = E->d_sweep_s; w.dbg = nullptr;
+  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns (1024 at bond 256, d = 4) per workgroup, every site
+  const int rc = stamp_buffer(E, s, (size_t)sd.J * R, &w.dbg);
+  if (rc != CTN_OK) return rc;
+  {
+    const dim3 gs((unsigned)sd.J, (unsigned)R);
+#define CTN_SWEEP_LAUNCH(DD)                                                                                      \
+    do {                                                                                                          \
+      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_f32<DD, 4>), gs, dim3(DD == 64 ? 256 : 512), 0, E->stream, w);  \
+      else hipLaunchKernelGGL((k_sweep_f32<DD, 2>), gs, dim3(DD == 64 ? 256 : 512), 0, E->stream, w);             \
+    } while (0)
+    if (sd.D == 64) CTN_SWEEP_LAUNCH(64);
+    else if (sd.D == 128) CTN_SWEEP_LAUNCH(128);
+    else if (sd.D == 256) CTN_SWEEP_LAUNCH(256);
+    else CTN_SWEEP_LAUNCH(512);
+#undef CTN_SWEEP_LAUNCH
+  }
+  const double numel = (double)P.tensors[st.out].numel;
+  hipLaunchKernelGGL(k_sweep_logs, dim3((unsigned)S, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
+                     (const float*)E->d_sweep_s, S, sd.J, E->d_sweep_la, E->d_sweep_ls);
+  hipLaunchKernelGGL(k_sweep_z, dim3((unsigned)S, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_la,
+                     (const double*)E->d_sweep_ls, S, sd.J, numel, E->d_sweep_z);
+  SweepFinish f{};
+  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.ls = E->d_sweep_ls; f.part_off = E->d_sweep_off;
+  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numel = numel;
+  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
+  hipLaunchKernelGGL(k_sweep_finish, dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+  return CTN_OK;
+}
+
+// a step of a sweep: the members before the last launch nothing, the last one launches the run
+static int launch_sweep_member(Exec* E, int s) {
+  if (E->sweep_role[s] == 1) return mark_absorbed(E, s);
+  const StepTimer t(E, s);
+  if (t.rc != CTN_OK) return t.rc;
+  const int rc = E->sweep.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
+  return rc != CTN_OK ? rc : t.end();
+}
+
+// a zipper pair in its latency form (k_zip_lat): steps (s - 1, s) as one launch, the result leaving as slabs
+static int launch_zip_lat(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const Exec::ZipLat& L = E->zl[s];
+  const Exec::ZipDesc& zd = L.d;
+  const Step& s1 = P.steps[s - 1];
+  const int S = ZM / L.mp, nub = zd.U / 16;
+  const bool eager = E->eager_rescale;
+  ZipLatArgs z{};
+  z.ptrs = E->d_ptrs; z.n_tensors = E->n_tensors;
+  z.idE = s1.lhs; z.idX = s1.rhs; z.idY = st.rhs;
+  z.slabs_in = (L.from_prev && !eager) ? E->d_zl_slab[L.buf ^ 1] : nullptr;
+  z.slabs_out = E->d_zl_slab[L.buf];
+  z.ldE = zd.ldE; z.ldXq = zd.ldXq; z.ldXk = zd.ldXk; z.ldYq = zd.ldYq; z.ldYm = zd.ldYm;
+  z.U = zd.U; z.R = R;
+  producer_partials(E, s1.lhs, &z.partE, &z.PE, &z.strideE, &z.numelE);
+  z.min_norm = P.min_norm;
+  z.partC = part_region(E, s);
+  z.partC_stride = E->step_partials[s];
+  const StepTimer t(E, s);
+  if (t.rc != CTN_OK) return t.rc;
+  report_tile(E, s, L.mp, ZM);      // (m1 part, all n2) per workgroup, 16 values of u
+  const dim3 gz((unsigned)((int64_t)R * nub * S));
+  z.dbg = nullptr;
+  const int rc = stamp_buffer(E, s, (size_t)gz.x, &z.dbg);
+  if (rc != CTN_OK) return rc;
+  if (zd.Q == 4 && L.mp == 32) hipLaunchKernelGGL((k_zip_lat<4, 32>), gz, dim3(512), 0, E->stream, z);
+  else if (zd.Q == 4) hipLaunchKernelGGL((k_zip_lat<4, 64>), gz, dim3(512), 0, E->stream, z);
+  else hipLaunchKernelGGL((k_zip_lat<2, 64>), gz, dim3(512), 0, E->stream, z);
+  if (!L.feeds_next || eager) {                 // nobody adds these slabs up while loading them: do it here
+    hipLaunchKernelGGL(k_zip_slab_sum, dim3((unsigned)E->step_partials[s], (unsigned)R), dim3(256), 0, E->stream,
+                       (const float*)z.slabs_out, S, zd.U, (void* const*)E->d_ptrs, E->n_tensors, st.out, zd.ldC, z.partC,
+                       z.partC_stride);
+    launch_renorm(E, s);
+  }
+  return t.end();
+}
+
+// Eager mode: normalise step s's result in place by the scale its partials give (the final tensor is normalised by k_finalize)
+static void launch_renorm(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  if (!E->eager_rescale || !P.stabilize || s + 1 >= P.n_steps) return;
+  const int out = P.steps[s].out;
+  const int64_t numel = P.tensors[out].numel;
+  const int V = P.dtype == CTN_F64 ? 2 : 4;
+  const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / V + 255) / 256, 2048)), E->R);
+  if (P.dtype == CTN_F32)
+    hipLaunchKernelGGL(k_renorm<float>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, out, numel,
+                       (const double*)part_region(E, s), E->step_partials[s], E->step_partials[s], P.min_norm);
+  else
+    hipLaunchKernelGGL(k_renorm<double>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, out, numel,
+                       (const double*)part_region(E, s), E->step_partials[s], E->step_partials[s], P.min_norm);
+}
+
+// The zipper-pair kernels by ctn_step_form: threads per workgroup, the tile ctn_exec_step_tile reports, and whether a
+// workgroup walks the launch's work items (grid from zipq_grid; else one workgroup per `zu` values of u and replica).
+// The tile is 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256): an fp64
+// step with 128 tile columns reads as k_mfma_f64_g.  k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a
+// wave sums; k_zipm64_f32 (bond 64) likewise (256, 32): its 256 threads, 32 values of m1 per wave - a tile no plain
+// form reports (theirs are 16 x 16 or have 64 columns at least)
+struct ZipKernel { void (*kernel)(ZipArgs); int threads, tm, tn; bool walks; };
+static const ZipKernel kZipKernels[] = {
+    {nullptr, 0, 0, 0, false},                // CTN_FORM_NONE
+    {k_zip_f32, 512, 512, 256, false},        // CTN_FORM_ZIP
+    {k_zipq_f32, 256, 512, 256, false},       // CTN_FORM_ZIPQ
+    {k_zip64_f32, 512, 512, 128, false},      // CTN_FORM_ZIP64
+    {k_zip128_f32, 512, 512, 64, false},      // CTN_FORM_ZIP128
+    {k_zipm64_f32, 256, 256, 32, false},      // CTN_FORM_ZIPM64
+    {k_zip_f64, 512, 512, 256, false},        // CTN_FORM_ZIP_F64
+    {k_zipqp_f32, 256, 512, 256, true},       // CTN_FORM_ZIPQP
+};
+static_assert(CTN_FORM_ZIP == 1 && CTN_FORM_ZIPQ == 2 && CTN_FORM_ZIP64 == 3 && CTN_FORM_ZIP128 == 4 && CTN_FORM_ZIPM64 == 5 &&
+              CTN_FORM_ZIP_F64 == 6 && CTN_FORM_ZIPQP == 7, "kZipKernels is indexed by ctn_step_form");
+
+// a zipper pair: steps (s - 1, s) as one launch
+static int launch_zip(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const Exec::ZipDesc& zd = E->zip[s];
+  const ZipKernel& zk = kZipKernels[zd.form];
+  const Step& s1 = P.steps[s - 1];
+  ZipArgs z{};
+  z.ptrs = E->d_ptrs; z.n_tensors = E->n_tensors;
+  z.idE = s1.lhs; z.idX = s1.rhs; z.idY = st.rhs; z.idC = st.out;
+  z.ldE = zd.ldE; z.ldXq = zd.ldXq; z.ldXk = zd.ldXk; z.ldYq = zd.ldYq; z.ldYm = zd.ldYm; z.ldC = zd.ldC;
+  z.K1 = zd.K1; z.Q = zd.Q; z.U = zd.U;
+  producer_partials(E, s1.lhs, &z.partE, &z.PE, &z.strideE, &z.numelE);
+  z.min_norm = P.min_norm;
+  z.partC = part_region(E, s);
+  z.partC_stride = E->step_partials[s];
+  z.R = R; z.dbg = nullptr;
+  z.n_items = (int32_t)zipq_items(R, zd.U, zd.zu);
+  const StepTimer t(E, s);
+  if (t.rc != CTN_OK) return t.rc;
+  E->launched_form[s] = zd.form;
+  report_tile(E, s, zk.tm, zk.tn);
+  const int per = zd.U / zd.zu;
+  const int rc = stamp_buffer(E, s, (size_t)per * R, &z.dbg);
+  if (rc != CTN_OK) return rc;
+  const int64_t wgs = zk.walks ? zipq_grid(z.n_items, E->n_cu, E->sw.zipq_wgs) : (int64_t)per * R;
+  hipLaunchKernelGGL(zk.kernel, dim3((unsigned)wgs), dim3(zk.threads), 0, E->stream, z);
+  launch_renorm(E, s);
+  return t.end();
+}
+
+// what the launch of a plain step leaves for its tail: partials in the scratch buffer that k_collapse folds
+struct Collapse { bool on; int blocks; };
+
+// A complex x complex step: the S step before it and this GEMM as one launch (k_cmfma_f32), reading `small`
+// and `big` as arrays of pairs; the scales are those of `small` (not of the never-written mid) and of `big`
+static int launch_cplx(Exec* E, int s, Collapse* col) {
+  const Plan& P = *E->plan;
+  const int R = E->R;
+  const CplxDesc& cd = E->cplx[s];
+  const int32_t* CT = E->d_cplx_tabs;
+  CplxArgs c{};
+  c.txr = CT + cd.txr; c.txk = CT + cd.txk; c.tyn = CT + cd.tyn; c.tyk = CT + cd.tyk; c.tcx = CT + cd.tcx; c.tcy = CT + cd.tcy;
+  c.ptrs = E->d_ptrs;
+  producer_partials(E, cd.small, &c.partX, &c.PX, &c.strideX, &c.numelX);
+  producer_partials(E, cd.big, &c.partY, &c.PY, &c.strideY, &c.numelY);
+  c.min_norm = P.min_norm;
+  c.Mx = cd.Mx; c.Ny = cd.Ny; c.Kc = cd.Kc;
+  c.idX = cd.small; c.idY = cd.big; c.idS = cd.sid; c.idC = P.steps[s].out; c.n_tensors = E->n_tensors;
+  c.tiles_x = (cd.Mx + CX_TX - 1) / CX_TX; c.tiles_y = (cd.Ny + CX_TY - 1) / CX_TY;
+  c.blocks_per_replica = c.tiles_x * c.tiles_y; c.R = R;
+  c.sa = cd.sa; c.sb = cd.sb; c.so = cd.so; c.sO = cd.sO; c.legx = cd.legx; c.legy = cd.legy;
+  c.c_vec2 = (cd.cvec2 && (s + 1 < P.n_steps || E->outs_aligned16)) ? 1 : 0;
+  col->on = c.blocks_per_replica > kMaxPartials;       // more workgroups than slots: through the collapse pass
+  col->blocks = c.blocks_per_replica;
+  c.partC = col->on ? E->d_scratch : part_region(E, s);
+  c.partC_stride = col->on ? col->blocks : E->step_partials[s];
+  report_tile(E, s, CX_TX, 2 * CX_TY);   // 64 pairs of `small` x (128 entries of `big` x 2 components): no plain form reports it
+  const dim3 gc((unsigned)((int64_t)c.blocks_per_replica * R));
+  if (cd.kfx && cd.kfy) hipLaunchKernelGGL((k_cmfma_f32<true, true>), gc, dim3(256), 0, E->stream, c);
+  else if (cd.kfx) hipLaunchKernelGGL((k_cmfma_f32<true, false>), gc, dim3(256), 0, E->stream, c);
+  else if (cd.kfy) hipLaunchKernelGGL((k_cmfma_f32<false, true>), gc, dim3(256), 0, E->stream, c);
+  else hipLaunchKernelGGL((k_cmfma_f32<false, false>), gc, dim3(256), 0, E->stream, c);
+  return CTN_OK;
+}
+
+// The left operand resident in registers, `ntw` column tiles per workgroup (k_mfma_f32_ares); one partial per
+// workgroup through the collapse pass the step has anyway
+static int launch_ares(Exec* E, int s, StepArgs& a, int ntw_av, Collapse* col) {
+  const Step& st = E->plan->steps[s];
+  const int ntw = ntw_av & 0xffff, avec = ntw_av >> 16;
+  const int wgs = (int)(st.Bt * (st.N / AR_TN / ntw));
+  a.partC = E->d_scratch; a.partC_stride = wgs;
+  col->on = true; col->blocks = wgs;
+  report_tile(E, s, 256, std::min(AR_TN * ntw, 32768));
+  const dim3 ga((unsigned)((int64_t)wgs * E->R));
+  if (st.modeB == 2) {
+    if (avec) hipLaunchKernelGGL((k_mfma_f32_ares<2, 1>), ga, dim3(512), 0, E->stream, a, ntw);
+    else hipLaunchKernelGGL((k_mfma_f32_ares<2, 0>), ga, dim3(512), 0, E->stream, a, ntw);
+  } else {
+    if (avec) hipLaunchKernelGGL((k_mfma_f32_ares<1, 1>), ga, dim3(512), 0, E->stream, a, ntw);
+    else hipLaunchKernelGGL((k_mfma_f32_ares<1, 0>), ga, dim3(512), 0, E->stream, a, ntw);
+  }
+  return CTN_OK;
+}
+
+// ---- the kinds of launch_form.h.  Each takes the step's arguments as fill_step_args left them and the form. ----
+
+// the slabs of a K split over workgroups, as the form laid them out
+static SplitKArgs slab_args(Exec* E, int s, const StepForm& f) {
+  const Plan& P = *E->plan;
+  SplitKArgs sk{};
+  sk.slab = E->d_slab;
+  sk.numelC = P.tensors[P.steps[s].out].numel;
+  sk.kchunk = f.kchunk;
+  sk.S = form_splits(P.steps[s], f);           // (empty trailing splits dropped)
+  return sk;
+}
+
+// k_mfma_f32_g on 256 x 128 tiles: hand-scheduled blocks for whole k-tiles, the C++ loop (which masks a ragged last
+// k-tile) otherwise
+static void launch_g_tiles(Exec* E, const Step& st, const StepArgs& a, bool use_asm) {
+  const dim3 gg((unsigned)((int64_t)a.blocks_per_replica * E->R));
+#define CTN_G_LAUNCH(AA, BB)                                                                             \
+  do {                                                                                                   \
+    if (use_asm) hipLaunchKernelGGL((k_mfma_f32_g<4, 2, true, AA, BB>), gg, dim3(256), 0, E->stream, a); \
+    else hipLaunchKernelGGL((k_mfma_f32_g<4, 2, false, AA, BB>), gg, dim3(256), 0, E->stream, a);        \
+  } while (0)
+  if (st.modeA == 2 && st.modeB == 1) CTN_G_LAUNCH(2, 1);
+  else if (st.modeA == 1 && st.modeB == 2) CTN_G_LAUNCH(1, 2);
+  else if (st.modeA == 2 || st.modeB == 2) CTN_G_LAUNCH(2, 2);
+  else CTN_G_LAUNCH(1, 1);
+#undef CTN_G_LAUNCH
+}
+
+static int launch_gsplitk(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const Step& st = E->plan->steps[s];
+  const SplitKArgs sk = slab_args(E, s, f);
+  a.ks_slab = sk.slab; a.ks_numelC = sk.numelC; a.ks_S = sk.S; a.ks_chunk = sk.kchunk;
+  launch_g_tiles(E, st, a, !E->sw.g_no_asm);           // (every split is whole k-tiles)
+  a.ks_slab = nullptr; a.ks_S = 0;
+  launch_splitk_reduce<float>(E, E->step_partials[s], E->R, a, sk);
+  return CTN_OK;
+}
+
+// one partial per tile, written directly
+static int launch_lat(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const dim3 g((unsigned)(f.blocks * E->R));
+  if (f.T == 16) hipLaunchKernelGGL((k_mfma_lat<16, float>), g, dim3(512), 0, E->stream, a, f.kchunk);
+  else if (f.T == 32) hipLaunchKernelGGL((k_mfma_lat<32, float>), g, dim3(512), 0, E->stream, a, f.kchunk);
+  else hipLaunchKernelGGL((k_mfma_lat<64, float>), g, dim3(512), 0, E->stream, a, f.kchunk);
+  return CTN_OK;
+}
+
+// one partial per tile (<= kMaxPartials)
+static int launch_h(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const Step& st = E->plan->steps[s];
+  const int rc = stamp_buffer(E, s, (size_t)f.blocks * E->R, &a.dbg);
+  if (rc != CTN_OK) return rc;
+  const dim3 gh((unsigned)(f.blocks * E->R));
+#define CTN_H_LAUNCH(AA, BB)                                                                        \
+  do {                                                                                              \
+    if (st.epw == 4) hipLaunchKernelGGL((k_mfma_f32_h<AA, BB, 4>), gh, dim3(512), 0, E->stream, a);      \
+    else if (st.epw == 2) hipLaunchKernelGGL((k_mfma_f32_h<AA, BB, 2>), gh, dim3(512), 0, E->stream, a); \
+    else hipLaunchKernelGGL((k_mfma_f32_h<AA, BB, 0>), gh, dim3(512), 0, E->stream, a);                  \
+  } while (0)
+  if (st.modeA == 2 && st.modeB == 2) CTN_H_LAUNCH(2, 2);
+  else if (st.modeA == 2) CTN_H_LAUNCH(2, 1);
+  else if (st.modeB == 2) CTN_H_LAUNCH(1, 2);
+  else CTN_H_LAUNCH(1, 1);
+#undef CTN_H_LAUNCH
+  return CTN_OK;
+}
+
+// the three throughput forms of an fp32 GEMM step: 256 x 256 and 256 x 128 tiles fed by LDS-DMA, register-staged tiles
+static int launch_tiles(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const Step& st = E->plan->steps[s];
+  static_assert(GM == 256 && GN == kTileN && GK == 16 && 2 * GK == 32, "planner eligibility rule (plan.cpp) assumes these");
+  const int rc = stamp_buffer(E, s, (size_t)st.blocks * E->R, &a.dbg);
+  if (rc != CTN_OK) return rc;
+  if (f.kind == Kind::G256)
+    hipLaunchKernelGGL((k_mfma_f32_g<8, 2, true>), dim3((unsigned)(f.blocks * E->R)), dim3(512), 0, E->stream, a);
+  else if (f.kind == Kind::G128)
+    launch_g_tiles(E, st, a, st.K % GK == 0 && !E->sw.g_no_asm);
+  else   // (halved tiles beyond the slots collapse; else the region has one slot per tile: step_form sized it by this form)
+    launch_mfma(st.modeA, st.modeB, f.tm, f.tn, dim3((unsigned)(f.blocks * E->R)), E->stream, a, E->sw);
+  return CTN_OK;
+}
+
+static int launch_lat64(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  hipLaunchKernelGGL((k_mfma_lat<16, double>), dim3((unsigned)(f.blocks * E->R)), dim3(512), 0, E->stream, a, f.kchunk);
+  return CTN_OK;
+}
+
+// the reduce pass of a K split over workgroups, in the plan's precision
+static void launch_reduce(Exec* E, int s, StepArgs& a, const SplitKArgs& sk) {
+  if (E->plan->dtype == CTN_F32) launch_splitk_reduce<float>(E, E->step_partials[s], E->R, a, sk);
+  else launch_splitk_reduce<double>(E, E->step_partials[s], E->R, a, sk);
+}
+
+// the latency mode of either precision: 64 x 64 tiles, K split over workgroups
+static int launch_splitk(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const Step& st = E->plan->steps[s];
+  SplitKArgs sk = slab_args(E, s, f);
+  sk.tiles_m = (int32_t)((st.M + 63) / 64);
+  sk.tiles_n = (int32_t)((st.N + 63) / 64);
+  sk.tiles_per_replica = (int32_t)(st.Bt * sk.tiles_m * sk.tiles_n);
+  const dim3 g((unsigned)(f.blocks * E->R));
+  if (f.kind == Kind::SplitK) launch_sk(st.modeA, st.modeB, g, E->stream, a, sk);
+  else launch_sk64(st.modeA, st.modeB, g, E->stream, a, sk);
+  launch_reduce(E, s, a, sk);
+  return CTN_OK;
+}
+
+// fp64 GEMM tiles: 128 x 128 fed by LDS-DMA (k_mfma_f64_g), or the planner's own 128 x 64
+static int launch_tiles64(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const Step& st = E->plan->steps[s];
+  const dim3 g((unsigned)(f.blocks * E->R)), b(256);
+  if (f.kind == Kind::G64) {
+    if (st.modeA == 2 && st.modeB == 2) hipLaunchKernelGGL((k_mfma_f64_g<2, 2>), g, b, 0, E->stream, a);
+    else if (st.modeA == 2) hipLaunchKernelGGL((k_mfma_f64_g<2, 1>), g, b, 0, E->stream, a);
+    else if (st.modeB == 2) hipLaunchKernelGGL((k_mfma_f64_g<1, 2>), g, b, 0, E->stream, a);
+    else hipLaunchKernelGGL((k_mfma_f64_g<1, 1>), g, b, 0, E->stream, a);
+    return CTN_OK;
+  }
+#define CTN_F64(AA, BB) hipLaunchKernelGGL((k_mfma_f64<AA, BB>), g, b, 0, E->stream, a)
+  switch (st.modeA * 3 + st.modeB) {
+    case 0: CTN_F64(0, 0); break; case 1: CTN_F64(0, 1); break; case 2: CTN_F64(0, 2); break;
+    case 3: CTN_F64(1, 0); break; case 4: CTN_F64(1, 1); break; case 5: CTN_F64(1, 2); break;
+    case 6: CTN_F64(2, 0); break; case 7: CTN_F64(2, 1); break; default: CTN_F64(2, 2); break;
+  }
+#undef CTN_F64
+  return CTN_OK;
+}
+
+static int launch_dot(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  if (f.kind == Kind::DotSplit) {
+    const SplitKArgs sk = slab_args(E, s, f);
+    const dim3 g((unsigned)f.blocks, R);
+    const Exec::DotTr dt = (int)E->dot_tr.size() == P.n_steps ? E->dot_tr[s] : Exec::DotTr();
+    if (P.dtype == CTN_F32) {
+      if (dt.on) hipLaunchKernelGGL(k_dot_tr<float>, g, dim3(256), 0, E->stream, a, (float*)sk.slab, sk.numelC, sk.S, dt.Ka, dt.Kb, dt.ldY, dt.x_is_a);
+      else hipLaunchKernelGGL(k_dot_split<float>, g, dim3(256), 0, E->stream, a, (float*)sk.slab, sk.numelC, sk.S, sk.kchunk);
+    } else {
+      if (dt.on) hipLaunchKernelGGL(k_dot_tr<double>, g, dim3(256), 0, E->stream, a, (double*)sk.slab, sk.numelC, sk.S, dt.Ka, dt.Kb, dt.ldY, dt.x_is_a);
+      else hipLaunchKernelGGL(k_dot_split<double>, g, dim3(256), 0, E->stream, a, (double*)sk.slab, sk.numelC, sk.S, sk.kchunk);
+    }
+    launch_reduce(E, s, a, sk);
+    return CTN_OK;
+  }
+  if (P.dtype == CTN_F32) hipLaunchKernelGGL(k_dot<float>, dim3(st.blocks, R), dim3(256), 0, E->stream, a);
+  else hipLaunchKernelGGL(k_dot<double>, dim3(st.blocks, R), dim3(256), 0, E->stream, a);
+  return CTN_OK;
+}
+
+// A streaming or row-dot step with its K split over workgroups (f.S > 0): the kernel writes slabs ...
+static SplitKArgs split_stream_args(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  SplitKArgs sk{};
+  if (f.S) {
+    sk = slab_args(E, s, f);
+    a.ks_slab = sk.slab; a.ks_numelC = sk.numelC; a.ks_S = sk.S; a.ks_chunk = sk.kchunk;
+  }
+  return sk;
+}
+
+// ... and the reduce pass writes the step's region itself
+static void reduce_split_stream(Exec* E, int s, StepArgs& a, const StepForm& f, const SplitKArgs& sk) {
+  if (!f.S) return;
+  a.partC = part_region(E, s); a.partC_stride = E->step_partials[s];
+  launch_reduce(E, s, a, sk);
+}
+
+static int launch_rowdot(Exec* E, int s, StepArgs& a, const StepForm& f) {
+  const SplitKArgs sk = split_stream_args(E, s, a, f);
+  const dim3 g(E->plan->steps[s].blocks, E->R, f.S ? sk.S : 1);
+  if (E->plan->dtype == CTN_F32) hipLaunchKernelGGL(k_rowdot<float>, g, dim3(256), 0, E->stream, a);
+  else hipLaunchKernelGGL(k_rowdot<double>, g, dim3(256), 0, E->stream, a);
+  reduce_split_stream(E, s, a, f, sk);
+  return CTN_OK;
+}
+
+static int launch_stream_kvec(Exec* E, int s, StepArgs& a) {
+  const dim3 g(E->plan->steps[s].blocks, E->R);
+  if (E->plan->dtype == CTN_F32) hipLaunchKernelGGL(k_stream_kvec<float>, g, dim3(256), 0, E->stream, a);
+  else hipLaunchKernelGGL(k_stream_kvec<double>, g, dim3(256), 0, E->stream, a);
+  return CTN_OK;
+}
+
+// the first enqueue of a leaf group: its steps' arguments are kept, the last one uploads and launches the group
+struct GroupCollect { int left = 0, head = -1; };
+
+static int launch_stream(Exec* E, int s, StepArgs& a, const StepForm& f, GroupCollect* gc) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  // vector stores need a 16-byte aligned destination: the caller's final buffer may not be
+  const int vw = (s + 1 == P.n_steps && !E->outs_aligned16) ? 1 : st.vecw;
+  int u;
+  int64_t nq;
+  stream_variant(st, E->R, vw, &u, &nq);
+  a.dNq = make_fastdiv(nq / u);
+  if (gc->left > 0) {
+    Exec::LeafGroup& G = E->groups[gc->head];
+    E->h_group_args[G.off + (s - gc->head)] = a;
+    if (--gc->left == 0) {
+      HIPCHECK(hipMemcpyAsync(E->d_group_args + G.off, E->h_group_args + G.off, sizeof(StepArgs) * G.len,
+                              hipMemcpyHostToDevice, E->stream));
+      G.ready = true;
+      launch_group(E, G);
+    }
+    return CTN_OK;
+  }
+  const SplitKArgs sk = split_stream_args(E, s, a, f);
+  const dim3 g(st.blocks, E->R, f.S ? sk.S : 1), b(256);
+#define CTN_STREAM(TT, VV, UU) hipLaunchKernelGGL((k_stream<TT, VV, UU>), g, b, 0, E->stream, a)
+  if (P.dtype == CTN_F32) {
+    if (vw == 4) { if (u == 4) CTN_STREAM(float, 4, 4); else CTN_STREAM(float, 4, 1); }
+    else { if (u == 4) CTN_STREAM(float, 1, 4); else CTN_STREAM(float, 1, 1); }
+  } else {
+    if (vw == 2) { if (u == 4) CTN_STREAM(double, 2, 4); else CTN_STREAM(double, 2, 1); }
+    else { if (u == 4) CTN_STREAM(double, 1, 4); else CTN_STREAM(double, 1, 1); }
+  }
+#undef CTN_STREAM
+  reduce_split_stream(E, s, a, f, sk);
+  return CTN_OK;
+}
+
+// A plain step: a pair or the resident-operand kernel where the executor found one, else the form step_form gives it
+// for this enqueue (the last step's depends on the caller's buffer); then the collapse pass and the eager rescale
+static int launch_step(Exec* E, int s, GroupCollect* gc) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  StepArgs a;
+  fill_step_args(E, s, &a);
+  const StepTimer t(E, s);
+  if (t.rc != CTN_OK) return t.rc;
+  const bool f32 = st.kernel == CTN_KERNEL_MFMA_F32;
+  if ((f32 || st.kernel == CTN_KERNEL_MFMA_F64) && (int64_t)st.blocks * E->R >= (1LL << 31)) { g_err = "grid too large"; return CTN_UNSUPPORTED; }
+  Collapse col{st.collapse, st.blocks};
+  int rc = CTN_OK;
+  if (f32 && !E->cplx.empty() && E->cplx[s].on) {
+    rc = launch_cplx(E, s, &col);
+  } else if (const int ntw_av = f32 && (int)E->ares_ntw.size() == P.n_steps ? E->ares_ntw[s] : 0) {
+    rc = launch_ares(E, s, a, ntw_av, &col);
+  } else {
+    const StepForm f = step_form(P, s, E->R, E->n_cu, E->sw, a.c_vec != 0);
+    col.on = f.collapse; col.blocks = (int)f.collapse_blocks;
+    if (f.tm) {   // an MFMA kind: the tile it reports; its tiling and where its partials go follow from the form
+      report_tile(E, s, f.tm, f.tn);
+      if (f.kind != Kind::SplitK && f.kind != Kind::SplitK64) {   // (those tile their slabs through SplitKArgs)
+        a.tiles_m = (int32_t)((st.M + f.tm - 1) / f.tm);
+        a.tiles_n = (int32_t)((st.N + f.tn - 1) / f.tn);
+        a.blocks_per_replica = (int32_t)f.blocks;
+      }
+      a.partC = f.collapse ? E->d_scratch : part_region(E, s);
+      a.partC_stride = f.collapse ? (int32_t)f.collapse_blocks : E->step_partials[s];
+    }
+    switch (f.kind) {
+      case Kind::None: break;                                              // (CTN_KERNEL_FUSED never gets here)
+      case Kind::GSplitK: rc = launch_gsplitk(E, s, a, f); break;
+      case Kind::Lat: rc = launch_lat(E, s, a, f); break;
+      case Kind::SplitK: case Kind::SplitK64: rc = launch_splitk(E, s, a, f); break;
+      case Kind::H: rc = launch_h(E, s, a, f); break;
+      case Kind::G256: case Kind::G128: case Kind::Plain: rc = launch_tiles(E, s, a, f); break;
+      case Kind::Lat64: rc = launch_lat64(E, s, a, f); break;
+      case Kind::G64: case Kind::Plain64: rc = launch_tiles64(E, s, a, f); break;
+      case Kind::Dot: case Kind::DotSplit: rc = launch_dot(E, s, a, f); break;
+      case Kind::RowDot: rc = launch_rowdot(E, s, a, f); break;
+      case Kind::StreamKvec: rc = launch_stream_kvec(E, s, a); break;
+      case Kind::Stream: rc = launch_stream(E, s, a, f, gc); break;
+    }
+  }
+  if (rc != CTN_OK) return rc;
+  if (col.on)
+    hipLaunchKernelGGL(k_collapse, dim3(E->R), dim3(256), 0, E->stream, (const double*)E->d_scratch, col.blocks, part_region(E, s));
+  launch_renorm(E, s);
+  return t.end();
+}
+
+// the scales of every step, then the final division
+static int launch_finish(Exec* E) {
+  const Plan& P = *E->plan;
+  const int R = E->R;
   FinalArgs f;
-  f.ptrs = E->d_ptrs;
-  f.partials = E->d_partials;
-  f.stepOff = E->d_stepOff;
-  f.stepSlots = E->d_stepSlots;
-  f.stepP = E->d_stepP;
-  f.stepNumel = E->d_stepNumel;
-  f.log_scale = E->d_log;
-  f.rescales = E->d_resc;
-  f.min_norm = P.min_norm;
-  f.out_numel = P.output().numel;
+  f.ptrs = E->d_ptrs; f.partials = E->d_partials; f.stepOff = E->d_stepOff; f.stepSlots = E->d_stepSlots;
+  f.stepP = E->d_stepP; f.stepNumel = E->d_stepNumel; f.log_scale = E->d_log; f.rescales = E->d_resc;
+  f.min_norm = P.min_norm; f.out_numel = P.output().numel;
   f.n_steps = P.n_steps; f.R = R; f.id_out = P.n_inputs + P.n_steps - 1; f.n_tensors = E->n_tensors;
   f.stabilize = P.stabilize ? 1 : 0;
   f.defer = E->defer_finish ? 1 : 0;
@@ -1762,6 +1414,42 @@ static int exec_launch_steps(Exec* E) {
     hipLaunchKernelGGL(k_finalize<double>, dim3(fb, R), dim3(256), 0, E->stream, f, (const double*)E->d_logs);
   }
   HIPCHECK(hipGetLastError());
+  return CTN_OK;
+}
+
+static int exec_launch_steps(Exec* E) {
+  const Plan& P = *E->plan;
+  int rc = CTN_OK;
+  if (P.chain && E->d_chain != nullptr) {
+    rc = launch_chain(E);
+  } else {
+    int group_skip = 0;
+    GroupCollect gc;
+    for (int s = 0; s < P.n_steps && rc == CTN_OK; ++s) {
+      if (group_skip > 0) { --group_skip; continue; }   // went out with the head of its group
+      if (gc.left == 0 && !E->groups.empty() && E->groups[s].len >= 2 && E->sw.group && !E->eager_rescale &&
+          !(E->timing_runs < E->timing_slots)) {
+        const Exec::LeafGroup& G = E->groups[s];
+        if (G.ready) {
+          launch_group(E, G);
+          group_skip = G.len - 1;
+          continue;
+        }
+        gc.left = G.len; gc.head = s;   // first time: the steps' arguments are built by launch_stream, not launched
+      }
+      if (!E->sweep_role.empty() && E->sweep_role[s] && !E->eager_rescale) rc = launch_sweep_member(E, s);
+      else if (!E->zl_skip.empty() && E->zl_skip[s]) rc = mark_absorbed(E, s);   // first step of a pair in its latency form
+      else if (!E->zl.empty() && E->zl[s].on) rc = launch_zip_lat(E, s);
+      else if (!E->zip_skip.empty() && E->zip_skip[s]) rc = mark_absorbed(E, s); // first step of a zipper pair
+      else if (!E->zip.empty() && E->zip[s].on) rc = launch_zip(E, s);
+      else if (!E->cplx_skip.empty() && E->cplx_skip[s]) rc = mark_absorbed(E, s);   // the S step of a complex pair
+      else if (P.steps[s].kernel == CTN_KERNEL_FUSED) rc = time_nothing(E, s);   // formed on the fly inside its consumer
+      else rc = launch_step(E, s, &gc);
+    }
+  }
+  if (rc != CTN_OK) return rc;
+  rc = launch_finish(E);
+  if (rc != CTN_OK) return rc;
   if (E->timing_runs < E->timing_slots) E->timing_runs++;
   return CTN_OK;
 }
@@ -1970,8 +1658,9 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   const Plan& P = plan->p;
   E.plan = &P; E.device = device; E.R = replicas; E.n_cu = n_cu > 0 ? n_cu : 256;
   E.sw = read_dev_switches();
-  E.mfma_g = E.sw.mfma_g;
   E.use_graph = E.sw.graph;
+  E.launched_tile.assign(P.n_steps, 0);
+  E.launched_form.assign(P.n_steps, 0);
   E.n_tensors = P.n_inputs + P.n_steps + 1;
   auto fail = [&](int code) { delete x; return code; };
 #define HIPCHECK_X(expr)                                                        \
@@ -1993,18 +1682,8 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   HIPCHECK_X(hipMalloc((void**)&E.d_ptrs, (size_t)replicas * E.n_tensors * sizeof(void*)));
   {
     size_t slab_elems = 0;   // split-K scratch: S slabs shaped like the step's output, per replica
-    // the splits the launcher will take, in its order: the large-tile split-K only on a step with a consumer (the
-    // final step goes on to the latency form, whose S can exceed the 16 slabs of the large-tile one)
-    auto splits_of = [&](int s) {
-      const Step& st = P.steps[s];
-      if (P.dtype == CTN_F32 && s + 1 < P.n_steps)
-        if (const int S = g_splitk(st, replicas, E.n_cu, E.mfma_g, E.sw, st.cvec)) return S;
-      if (lat_form(st, replicas, E.n_cu, P.dtype, E.sw)) return 0;
-      if (const int S = splitk_splits(st, replicas, E.n_cu, P.dtype, E.sw)) return S;
-      if (const int S = dot_splits(st)) return S;
-      if (const int S = stream_splits(st, replicas, E.n_cu)) return S;
-      return rowdot_splits(st, replicas, E.n_cu);
-    };
+    // the splits the launcher will take: it asks step_form too, and the answer does not depend on the caller's buffers
+    auto splits_of = [&](int s) { return step_form(P, s, replicas, E.n_cu, E.sw, P.steps[s].cvec).S; };
     for (int s = 0; s < P.n_steps; ++s)
       if (const int S = splits_of(s))
         slab_elems = std::max(slab_elems, (size_t)S * (size_t)P.tensors[P.steps[s].out].numel * (size_t)replicas);
@@ -2025,23 +1704,10 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
     const Step& st = P.steps[s];
     E.step_partials[s] = std::max(st.partials, 1);
     if (P.chain) { E.step_off[s] = E.part_slots++; continue; }   // the chain walker: one slot per step, whatever the kernel kind
-    if (E.d_slab && P.dtype == CTN_F32 && s + 1 < P.n_steps && g_splitk(st, replicas, E.n_cu, E.mfma_g, E.sw, st.cvec))
-      E.step_partials[s] = (int)std::max<int64_t>(1, std::min<int64_t>(kWaveOutputs, P.tensors[st.out].numel / 1024));
-    else if (const int T = lat_form(st, replicas, E.n_cu, P.dtype, E.sw))
-      E.step_partials[s] = (int)(st.Bt * ((st.M + T - 1) / T) * ((st.N + T - 1) / T));
-    else if (E.d_slab && (splitk_splits(st, replicas, E.n_cu, P.dtype, E.sw) || dot_splits(st) || stream_splits(st, replicas, E.n_cu) ||
-                          rowdot_splits(st, replicas, E.n_cu)))
-      E.step_partials[s] = (int)std::max<int64_t>(1, std::min<int64_t>(kWaveOutputs, P.tensors[st.out].numel / 1024));
-    else if (!g_launch(st, replicas, E.n_cu, E.mfma_g) && s + 1 < P.n_steps &&
-             h_form(P, st, replicas, E.n_cu, P.dtype, E.sw, st.cvec))
-      E.step_partials[s] = (int)(st.Bt * ((st.M + 127) / 128) * ((st.N + 127) / 128));
-    else if (st.kernel == CTN_KERNEL_MFMA_F32 && !st.collapse) {
-      int tm, tn;
-      plain_tiles(st, replicas, E.n_cu, E.mfma_g, s + 1 == P.n_steps, &tm, &tn, E.sw.halve);
-      const int64_t tiles = st.Bt * ((st.M + tm - 1) / tm) * ((st.N + tn - 1) / tn);
-      E.step_partials[s] = tiles > kMaxPartials ? 1 : (int)tiles;     // halved tiles beyond the slots: collapsed at launch
-      scratch_need = std::max<int64_t>(scratch_need, tiles);
-    }
+    // (a step with S > 0 has made d_slab non-null just above, and the launcher drops no split for want of it)
+    const StepForm f = step_form(P, s, replicas, E.n_cu, E.sw, st.cvec);
+    E.step_partials[s] = f.partials;
+    scratch_need = std::max<int64_t>(scratch_need, f.collapse_blocks);
     E.step_off[s] = E.part_slots;
     E.part_slots += E.step_partials[s];
   }
@@ -2068,7 +1734,7 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
         const int64_t wgs = (int64_t)(z.U / ZDU) * replicas;
         if (E.sw.zip != 1 && !(kZipF64Default && wgs >= E.n_cu && fill(wgs) >= 0.9)) continue;
         if (z.U / ZDU > kMaxPartials) continue;
-        z.zu = ZDU;
+        z.zu = ZDU; z.form = CTN_FORM_ZIP_F64;
         E.zip[s] = z;
         E.zip_skip[s - 1] = 1;
         any = true;
@@ -2082,18 +1748,20 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
                        (E.sw.zip == 2 || (int64_t)(z64.U / Z6U) * replicas >= E.n_cu);
       const double f128 = m128 ? fill((int64_t)(z128.U / ZU) * replicas) : 0.0, f64 = m64 ? fill((int64_t)(z64.U / Z6U) * replicas) : 0.0;
       bool ok = false;
-      if (m128 && (E.sw.zip == 1 || f128 >= 0.9 || f128 >= f64)) { ok = true; z = z128; z.zu = ZU; }
-      else if (m64 && (E.sw.zip == 2 || f64 >= 0.9)) { ok = true; z = z64; z.zu = Z6U; }
-      else if (m128) { ok = true; z = z128; z.zu = ZU; }
+      if (m128 && (E.sw.zip == 1 || f128 >= 0.9 || f128 >= f64)) { ok = true; z = z128; z.zu = ZU; z.form = CTN_FORM_ZIP; }
+      else if (m64 && (E.sw.zip == 2 || f64 >= 0.9)) { ok = true; z = z64; z.zu = Z6U; z.form = CTN_FORM_ZIP64; }
+      else if (m128) { ok = true; z = z128; z.zu = ZU; z.form = CTN_FORM_ZIP; }
       // the 128-u form with two legs per pass (k_zipq_f32): on request wherever the pair matches (CTN_ZIPQ=1, also where
       // the rules above chose otherwise - but not against CTN_ZIP=2), else under k_zip_f32's own default rule
       // ... and its walking form (k_zipqp_f32): on request (CTN_ZIPQ=2) wherever CTN_ZIPQ=1 takes k_zipq_f32, else under
       // kZipQPDefault where that kernel is taken by default and has two rounds of workgroups at least
       if ((E.sw.zipq == 1 || E.sw.zipq == 2) && E.sw.zip != 2 && zip_match(P, s, &z128, CTN_F32) && zipq_fits(z128)) {
         ok = true; z = z128; z.zu = ZU; z.zq = true; z.zqp = E.sw.zipq == 2;
+        z.form = z.zqp ? CTN_FORM_ZIPQP : CTN_FORM_ZIPQ;
       } else if (E.sw.zipq == -1 && kZipQDefault && E.sw.zip == -1 && ok && z.zu == ZU && f128 >= 0.9 && zipq_fits(z)) {
         z.zq = true;
         z.zqp = kZipQPDefault && zipq_items(replicas, z.U, ZU) >= 2 * (int64_t)E.n_cu;
+        z.form = z.zqp ? CTN_FORM_ZIPQP : CTN_FORM_ZIPQ;
       }
       // bond 128 (k_zip128_f32: 128 values of u per workgroup, K1 a multiple of its tile depth and two tiles at least -
       // ZK = Z1K, as zip_match checks), when no bond-256 form matches: only on request (CTN_ZIP=1, and not CTN_ZIP128=0).
@@ -2103,7 +1771,7 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       if (!m128 && !m64 && E.sw.zip128 != 0 && E.sw.zip != 0 && E.sw.zip != 2 && zip_match(P, s, &z, CTN_F32, Z1U, Z1M) &&
           z.K1 % Z1K == 0 && z.K1 >= 2 * Z1K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
           (E.sw.zip == 1 || (kZip128Default && (int64_t)(z.U / Z1U) * replicas >= E.n_cu && fill((int64_t)(z.U / Z1U) * replicas) >= 0.9))) {
-        ok = true; z.zu = Z1U; z.zm = Z1M;
+        ok = true; z.zu = Z1U; z.zm = Z1M; z.form = CTN_FORM_ZIP128;
       }
       // bond 64 (k_zipm64_f32: 64 values of u per workgroup, the same tile depth), when neither a bond-256 nor the bond-128
       // form matches: only on request (CTN_ZIP=1, and not CTN_ZIPM64=0).  kZipM64Default as kZip128Default: the
@@ -2112,7 +1780,7 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       if (!ok && E.sw.zipm64 != 0 && E.sw.zip != 0 && E.sw.zip != 2 && zip_match(P, s, &z, CTN_F32, Z4U, Z4M) &&
           z.K1 % Z4K == 0 && z.K1 >= 2 * Z4K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
           (E.sw.zip == 1 || (kZipM64Default && (int64_t)(z.U / Z4U) * replicas >= E.n_cu && fill((int64_t)(z.U / Z4U) * replicas) >= 0.9))) {
-        ok = true; z.zu = Z4U; z.zm = Z4M;
+        ok = true; z.zu = Z4U; z.zm = Z4M; z.form = CTN_FORM_ZIPM64;
       }
       if (!ok || z.U / z.zu > kMaxPartials) continue;    // (one abs-sum partial per workgroup: the consumers add at most that many)
       E.zip[s] = z;
