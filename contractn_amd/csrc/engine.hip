@@ -14,6 +14,11 @@
 //     consumer (or the finishing pass) reduces <= 64 partials with one wave in a
 //     fixed order, so results are bit-reproducible run to run (no float atomics).
 //
+// What runs where is decided in host-only headers: launch_form.h (step_form(): the kernel of a plain step, asked at
+// creation and on every launch) and fused_forms.h (fused_forms(): the fused launches, every step's role in them and the
+// layout of the partial sums, decided once in ctn_exec_create, which then only allocates).  The launch_<form> functions
+// below read those records and launch.
+//
 // Written for CDNA4 only: 64-lane waves, v_mfma_f32_32x32x2_f32, 160 KiB LDS/CU.
 #include <hip/hip_runtime.h>
 
@@ -28,6 +33,7 @@
 #include "plan.h"
 #include "chain_pack.h"
 #include "cplx_match.h"
+#include "fused_forms.h"
 #include "grad_tape.h"
 #include "launch_form.h"
 
@@ -63,6 +69,10 @@ thread_local std::string g_err;
 
 static_assert(kFormGM == GM && kFormGK == GK && kFormDN == DN && kFormLatMaxK == kLatMaxK,
               "launch_form.h selects kernels by these values of theirs");
+static_assert(kFormZM == ZM && kFormZU == ZU && kFormZK == ZK && kFormZDU == ZDU && kFormZDK == ZDK && kFormZ6U == Z6U && kFormZ6K == Z6K &&
+                  kFormZ1M == Z1M && kFormZ1U == Z1U && kFormZ1K == Z1K && kFormZ4M == Z4M && kFormZ4U == Z4U && kFormZ4K == Z4K &&
+                  kFormSWR == SWR && kFormSweepMaxSites == kSweepMaxSites && kFormArM == AR_M && kFormArK == AR_K && kFormArTN == AR_TN,
+              "fused_forms.h matches plans against these values of theirs");
 
 #define HIPCHECK(expr)                                                                  \
   do {                                                                                   \
@@ -101,50 +111,13 @@ struct Exec {
   bool graph_warm = false;          // one eager enqueue has run (code objects loaded, tiles recorded)
   bool graph_aligned = true;        // outs_aligned16 the graph was captured under
   hipGraphExec_t graph_exec = nullptr;
-  // zipper pairs (kernels_zip.h): zip[s2] describes the fused launch of steps (s2 - 1, s2); zip_skip[s1] = the first
-  // step of such a pair is never launched (its result only exists in the fused kernel's registers)
-  struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
-                   int zu = 128; bool f64 = false;      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
-                   int zm = 256;
-                   bool zq = false, zqp = false;        // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even); zqp: as k_zipqp_f32                     // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
-                   int form = CTN_FORM_NONE; };         // the kernel that runs the pair (ctn_step_form), set where it is chosen
-  std::vector<ZipDesc> zip;
-  std::vector<char> zip_skip;
-  // k_zipqp_f32 only: results that the plan's workspace puts where the pair's own E lies (the planner frees E at the
-  // pair's first step, and first fit hands its bytes to E') live in side buffers instead - zqp_side[id] = which one, or -1.
-  // A workgroup of k_zipq_f32 stores its rows of E' when every workgroup of the replica has long read E; a workgroup
-  // that goes on to the replica's next block of u has not.
-  char* d_zqp_side = nullptr;
-  std::vector<int> zqp_side;
-  int64_t zqp_side_bytes = 0;       // one replica's part of one side buffer
-  // the same pairs in their latency form (kernels_zipl.h): zl[s2] = the fused launch of steps (s2 - 1, s2), whose result
-  // leaves as slabs; from_prev = its E is the slabs of the pair before, feeds_next = the next pair adds its slabs up (else
-  // k_zip_slab_sum does); zl_skip[s1] like zip_skip
-  struct ZipLat { bool on = false, from_prev = false, feeds_next = false; int buf = 0, mp = 32; ZipDesc d; };
-  std::vector<ZipLat> zl;
-  std::vector<char> zl_skip;
-  float* d_zl_slab[2] = {nullptr, nullptr};   // [R][S][U][ZM] each, ping-pong along the chain
-  // complex x complex step pairs (kernels_cmfma.h): cplx[s] describes the fused launch of step s, a GEMM, with the S step
-  // that produces its operand; cplx_skip[that step] = the S step is never launched (the widened operand only exists in registers).
-  // (CplxDesc: cplx_match.h; its t* fields are offsets of the pair-granular tables inside d_cplx_tabs)
-  std::vector<CplxDesc> cplx;
-  std::vector<char> cplx_skip;
-  int32_t* d_cplx_tabs = nullptr;
-  // a sweep (kernels_sweep.h): a run of epilogue-summed GEMM steps, each on the result of the one before, walked by ONE
-  // launch at the position of its last member; sweep_role[s] = 1 a member that is never launched, 2 the last member
-  struct SweepDesc {
-    bool on = false;
-    std::vector<int> steps;          // the members' step indices, in chain order
-    int64_t ldIn = 0, ldOut = 0, ldWl = 0, ldWp = 0, ldX = 0;
-    int J = 0, M = 0, D = 0, Pd = 0;     // row blocks, rows, bond and physical dimension
-    // float64 (kernels_sweep_f64.h): the members are the 2 S steps of S sites - (GEMM, streaming sum over p) pairs, both
-    // reporting a rescale factor; ids = [S][2] tensor ids (W_s, x_s), idIn the chain's input E
-    bool f64 = false;
-    int idIn = -1;
-    std::vector<int32_t> ids;
-  };
-  SweepDesc sweep;
-  std::vector<char> sweep_role;
+  // Every fused launch the executor takes, each step's role in them, the layout of the partial sums and the sizes of
+  // the buffers below: decided by fused_forms() (fused_forms.h) when the executor is created, read ever after.
+  FusedForms forms;
+  char* d_zqp_side = nullptr;          // k_zipqp_f32: [forms.zqp_side_bufs][R] side buffers of forms.zqp_side_bytes
+  float* d_zl_slab[2] = {nullptr, nullptr};   // latency pairs: [R][S][U][ZM] each, ping-pong along the chain
+  int32_t* d_cplx_tabs = nullptr;      // complex pairs: forms.cplx_tabs
+  // the sweep's tables and records
   int32_t* d_sweep_ids = nullptr;      // [S][2] tensor ids (W_s, x_s)
   int64_t* d_sweep_off = nullptr;      // [S] step_off of the members
   int32_t* d_sweep_slots = nullptr;    // [S] step_partials of the members
@@ -154,12 +127,6 @@ struct Exec {
   double* d_sweep_la = nullptr;        // [R][S][J] logs of d_sweep_a / d_sweep_s
   double* d_sweep_ls = nullptr;
   int32_t* d_sweep_e = nullptr;        // float64: [R][S][J] exponents of the blocks' scales (d_sweep_a: [R][2 S][J], d_sweep_z: [R][2 S])
-  // steps with a small resident left operand against a very wide right one (kernels_mfma_ares.h): column tiles per workgroup
-  // (bit 16: the left operand takes 16-byte loads), 0 = not taken
-  std::vector<int> ares_ntw;
-  // full dots of a tensor with a transposed one (k_dot_tr), found on the plan's tables when the executor is created
-  struct DotTr { bool on = false; int Ka = 0, Kb = 0, x_is_a = 1; int64_t ldY = 0; };
-  std::vector<DotTr> dot_tr;
   std::vector<int32_t> launched_form;  // per step: ctn_step_form of the last enqueue (ctn_exec_step_form), else 0
   std::vector<int32_t> launched_tile;  // per step: (tile rows << 16 | tile columns) of the last enqueue's MFMA kernel, else 0
   char* d_ws = nullptr;
@@ -172,10 +139,7 @@ struct Exec {
   double* d_scratch = nullptr;
   void* d_slab = nullptr;           // split-K partial tiles (latency mode), sized at creation
   void* d_slab2 = nullptr;          // 1/16 of it: where more than 16 slabs are folded 16 to 1 (k_splitk_fold)
-  std::vector<int> step_partials;   // abs-sum partials per replica of every step (plan value unless split-K / latency form)
-  std::vector<int64_t> step_off;    // d_partials: step s, replica r at (step_off[s] * R + r * step_partials[s]) doubles
-  int64_t part_slots = 0;           // sum of the steps' slots
-  int64_t* d_stepOff = nullptr;
+  int64_t* d_stepOff = nullptr;     // forms.step_off and forms.step_partials
   int32_t* d_stepSlots = nullptr;
   double* d_log = nullptr;
   double* d_resc = nullptr;
@@ -203,11 +167,7 @@ struct Exec {
   int eager_reruns = 0;
   int eager_streak = 0;             // consecutive runs that had to be repeated eagerly (see exec_new_run)
   std::vector<double> h_resc;       // host copy of the last run's per-step rescale factors [R][n_steps]
-  // Grouped leaf steps: runs of consecutive streaming steps whose operands are all network inputs (independent of
-  // each other and of everything before them) go out as ONE launch of k_stream_group; their arguments never
-  // change, so they are built on the first enqueue and kept in device memory.
-  struct LeafGroup { int len = 0, vw = 1, u = 1, blocks = 1, off = 0; bool ready = false; };
-  std::vector<LeafGroup> groups;    // per step: len >= 2 at the head of a group, else 0
+  // the leaf groups' arguments (forms.groups, forms.group_args records), built on the first enqueue
   StepArgs* h_group_args = nullptr; // pinned: the one-time upload may fall inside a stream capture
   StepArgs* d_group_args = nullptr;
   bool defer_finish = false;        // ctn_exec_set_finish_mode(1): the final division waits for ctn_exec_finish
@@ -367,359 +327,10 @@ static void launch_splitk_reduce(Exec* E, int partials, int R, const StepArgs& a
   hipLaunchKernelGGL(k_splitk_reduce<T>, dim3(partials, R), dim3(256), 0, E->stream, a, sk);
 }
 
-// Is k_zip_f64 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
-static constexpr bool kZipF64Default = false;
-// Is k_zip128_f32 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
-static constexpr bool kZip128Default = false;
-// Is k_zipm64_f32 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
-static constexpr bool kZipM64Default = false;
-
-// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32; `zm` = 128: k_zip128_f32, 64: k_zipm64_f32) or k_zip_f64 (CTN_F64)
-// can run as one launch?
-// Checked on the plan's own offset tables (every operand dense along its innermost index with uniform strides), so
-// nothing about the network's labels is assumed: T = E . X with |m1| = zm rows from E, columns (q, u) from X;
-// E' = T . Y contracting (m1, q), |n2| = zm.  The element type decides the kernel kind of the two steps, the depth of a
-// phase-1 tile and - fp64: 16-byte requests and stores of pairs of doubles - that every leading dimension is even.
-static bool zip_match(const Plan& P, int s2, Exec::ZipDesc* z, int dtype, int u_mult = ZU, int zm = ZM) {
-  if (s2 < 1 || s2 + 1 >= P.n_steps || P.dtype != dtype || (dtype != CTN_F32 && dtype != CTN_F64)) return false;
-  const bool f64 = dtype == CTN_F64;
-  const int kt = f64 ? ZDK : ZK;
-  const Step& a = P.steps[s2 - 1];
-  const Step& b = P.steps[s2];
-  auto plain = [&](const Step& st) {
-    return st.kernel == (f64 ? CTN_KERNEL_MFMA_F64 : CTN_KERNEL_MFMA_F32) && st.Bt == 1 && st.rhs >= 0 && st.lhs2 < 0 && !st.epw && st.modeA == 1 &&
-           st.modeB == 1 && !st.collapse;
-  };
-  if (!plain(a) || !plain(b) || b.lhs != a.out || !b.cvec) return false;
-  if (a.rhs >= P.n_inputs || b.rhs >= P.n_inputs) return false;            // X and Y: network inputs (scale 1)
-  if (a.M != zm || b.N != zm || a.K % kt != 0 || a.K < 2 * kt || a.N % u_mult != 0) return false;
-  const int32_t* T = P.tables.data();
-  const int32_t *omA = T + a.t.omA, *okA = T + a.t.okA, *onB = T + a.t.onB, *okB = T + a.t.okB, *omC = T + a.t.omC, *onC = T + a.t.onC;
-  const int64_t N1 = a.N;
-  for (int i = 0; i < zm; ++i) if (omA[i] != i || omC[i] != (int64_t)i * N1) return false;     // E rows dense, T = [m1][N1]
-  for (int64_t n = 0; n < N1; ++n) if (onC[n] != n) return false;
-  int64_t U = N1;
-  for (int64_t n = 1; n < N1; ++n) if (onB[n] != onB[0] + n) { U = n; break; }
-  if (onB[0] != 0 || U % u_mult != 0 || N1 % U != 0) return false;
-  const int64_t Q = N1 / U, ldXq = Q > 1 ? onB[U] : 0;
-  for (int64_t n = 0; n < N1; ++n) if (onB[n] != (n / U) * ldXq + n % U) return false;
-  const int64_t ldE = okA[1] - okA[0], ldXk = okB[1] - okB[0];
-  for (int64_t k = 0; k < a.K; ++k) if (okA[k] != k * ldE || okB[k] != k * ldXk) return false;
-  if (ldE < zm || b.M != U || b.K != (int64_t)zm * Q) return false;
-  const int32_t *omA2 = T + b.t.omA, *okA2 = T + b.t.okA, *onB2 = T + b.t.onB, *okB2 = T + b.t.okB, *omC2 = T + b.t.omC, *onC2 = T + b.t.onC;
-  for (int64_t u = 0; u < U; ++u) if (omA2[u] != u) return false;                                   // T dense along u
-  for (int i = 0; i < zm; ++i) if (onB2[i] != i || onC2[i] != i) return false;
-  const int64_t ldC = U > 1 ? omC2[1] - omC2[0] : zm;
-  for (int64_t u = 0; u < U; ++u) if (omC2[u] != u * ldC) return false;
-  if (ldC < zm) return false;
-  // the contracted group of the second step enumerates (m1, q) in some order: read each entry's (m1, q) off T's offset
-  int64_t ldYm = -1, ldYq = Q > 1 ? -1 : 0;
-  for (int64_t k = 0; k < b.K; ++k) {
-    const int64_t off = okA2[k], m1 = off / N1, q = (off % N1) / U;
-    if (off % U != 0 || m1 >= zm) return false;
-    if (m1 == 1 && q == 0) ldYm = okB2[k];
-    if (m1 == 0 && q == 1) ldYq = okB2[k];
-  }
-  if (ldYm < zm || ldYq < 0) return false;
-  std::vector<char> seen((size_t)b.K, 0);
-  for (int64_t k = 0; k < b.K; ++k) {
-    const int64_t off = okA2[k], m1 = off / N1, q = (off % N1) / U;
-    if (okB2[k] != q * ldYq + m1 * ldYm || seen[(size_t)(m1 * Q + q)]) return false;
-    seen[(size_t)(m1 * Q + q)] = 1;
-  }
-  if (f64 && ((ldE | ldXq | ldXk | ldYq | ldYm | ldC) & 1)) return false;
-  z->on = true; z->f64 = f64; z->ldE = ldE; z->ldXq = ldXq; z->ldXk = ldXk; z->ldYq = ldYq; z->ldYm = ldYm; z->ldC = ldC;
-  z->Q = (int)Q; z->U = (int)U; z->K1 = (int)a.K;
-  return true;
-}
-
-// Is k_zipq_f32 taken without CTN_ZIPQ=1 where k_zip_f32 would be by its own default rule (fp32, one round of workgroups at
-// least, rounds filled)?  Decided by measurement: +3.3 % on the headline at R = 512, +3.0 % at 128, +3.1 % at 256,
-// fourteen times the larger spread.
-static constexpr bool kZipQDefault = true;
-// Can k_zipq_f32 run a pair that zip_match took for k_zip_f32?  Its legs go in pairs, and its LDS-DMA requests address
-// every operand with an unsigned 32-bit byte offset off the tensor's base.
-// Of the two forms of that kernel, is k_zipqp_f32 (a workgroup walks its work items; kernels_zipqp.h) taken without
-// CTN_ZIPQ=2 where the rule above takes k_zipq_f32 and the launch has two rounds of workgroups at least (fewer: nothing
-// to walk)?  Decided by measurement: +1.7 % on the headline at R = 512 (5,302.8 -> 5,391.9 contractions/s,
-// spreads 7.9 and 5.0: eleven times the larger), +2.0 % at R = 256; the same bits.
-static constexpr bool kZipQPDefault = true;
-static bool zipq_fits(const Exec::ZipDesc& z) {
-  const int64_t lim = (int64_t)1 << 31;
-  return z.Q >= 2 && z.Q % 2 == 0 && (int64_t)z.K1 * z.ldE * 4 < lim && ((int64_t)z.Q * z.ldXq + (int64_t)z.K1 * z.ldXk + z.U) * 4 < lim &&
-         ((int64_t)z.Q * z.ldYq + (int64_t)ZM * z.ldYm) * 4 < lim;
-}
-
-// Is k_cmfma_f32 taken without CTN_CPLX=1 wherever cplx_match takes a pair?  Decided by measurement (DESIGN sections 10
-// and 11): tools/cplx_step_timing.py has to show the fused form ahead of the two launches by more than the larger spread
-// at every one of its shapes, and the complex GPU suite has to be green with CTN_CPLX=1.
-static constexpr bool kCplxDefault = false;
-
 // Is a chain plan walked by k_chain_lds without CTN_CHAIN=2 wherever chain_pack accepts it?  Decided by measurement
 // (DESIGN sections 10 and 11): tools/chain_timing.py has to show it ahead of k_chain by more than the larger spread at
 // every workload it measures, and the whole suite has to be green with it on.  Results are bit-identical either way.
 static constexpr bool kChainLdsDefault = false;
-
-// Is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
-// offset tables: E row-major [b][l], W[l][p][r] with r unit-stride, x[b][p] with p unit-stride, result rows [b][r].
-struct SweepShape { int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
-static bool sweep_step_shape(const Plan& P, int s, SweepShape* sh) {
-  const Step& st = P.steps[s];
-  const int D = (int)st.K, Pd = st.epw;
-  if (P.dtype != CTN_F32 || st.kernel != CTN_KERNEL_MFMA_F32 || (Pd != 2 && Pd != 4) || st.Bt != 1 ||
-      (st.K != 64 && st.K != 128 && st.K != 256 && st.K != 512) || st.N != (int64_t)D * Pd || s + 1 >= P.n_steps)
-    return false;
-  // (st.collapse - the step's OWN launch would have more workgroups than partial slots and leave one collapsed slot - is
-  // no obstacle: a member is never launched, and k_sweep_finish fills however many slots the step has, slot 0 first)
-  if (st.rhs < 0 || st.rhs >= P.n_inputs || st.lhs2 < 0 || st.lhs2 >= P.n_inputs) return false;   // W, x: network inputs
-  const int32_t* T = P.tables.data();
-  const int32_t *omA = T + st.t.omA, *okA = T + st.t.okA, *onB = T + st.t.onB, *okB = T + st.t.okB, *omC = T + st.t.omC,
-                *onC = T + st.t.onC, *omX = T + st.t.omA2;
-  const int64_t M = st.M;
-  const int64_t ldA = M > 1 ? omA[1] : D, ldC = M > 1 ? omC[1] : D, ldX = M > 1 ? omX[1] : Pd, ldWl = okB[1];
-  for (int64_t m = 0; m < M; ++m)
-    if (omA[m] != m * ldA || omC[m] != m * ldC || omX[m] != m * ldX) return false;
-  for (int k = 0; k < D; ++k)
-    if (okA[k] != k || okB[k] != (int64_t)k * ldWl) return false;
-  int64_t ldWp = INT64_MAX;
-  for (int n = 0; n < D * Pd; ++n)
-    if (onB[n] >= D) ldWp = std::min<int64_t>(ldWp, onB[n]);
-  if (ldWp == INT64_MAX) return false;
-  std::vector<char> seen((size_t)D * Pd, 0);
-  for (int n = 0; n < D * Pd; ++n) {
-    const int64_t off = onB[n], pp = off / ldWp, rr = off % ldWp;
-    if (off < 0 || pp >= Pd || rr >= D || onC[n] != rr || seen[(size_t)(pp * D + rr)]) return false;
-    seen[(size_t)(pp * D + rr)] = 1;
-  }
-  if (ldA < D || ldC < D || ldA % 4 || ldC % 4 || ldX % Pd || ldX < Pd || ldWl % 4 || ldWp % 4 || ldWl < D) return false;
-  if (((D + 12) * ldWl + 3 * ldWp + D) * 4 >= ((int64_t)1 << 31)) return false;   // a lane's offsets into a core: 32 bits
-  sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = D; sh->Pd = Pd;
-  return true;
-}
-
-// The longest run of such steps, each taking the result of the one before as its E.
-static bool sweep_match(const Plan& P, Exec::SweepDesc* d) {
-  std::vector<int> best;
-  SweepShape best_first, best_last;
-  std::vector<char> used((size_t)P.n_steps, 0);
-  for (int s0 = 0; s0 < P.n_steps; ++s0) {
-    SweepShape first, cur, last;
-    if (used[s0] || !sweep_step_shape(P, s0, &first)) continue;
-    std::vector<int> run{s0};
-    last = first;
-    for (int s = s0 + 1; s < P.n_steps; ++s) {
-      // Only markers of absorbed steps (nothing is launched for them) may lie between two members: the ONE launch of
-      // the run sits at its last member's position and reads the first member's input there, which the plan's arena
-      // released right after the first member - any launched step in between (the other half of an interleaved
-      // left / right chain, say) could have been given that region.  Such a step ends the run.
-      if (P.steps[s].kernel == CTN_KERNEL_FUSED) continue;
-      if (P.steps[s].lhs != P.steps[run.back()].out && P.steps[s].rhs != P.steps[run.back()].out &&
-          P.steps[s].lhs2 != P.steps[run.back()].out)
-        break;
-      // the consumer of the run's last result: a member if it has the same shape and takes it as its E
-      if (P.steps[s].lhs == P.steps[run.back()].out && sweep_step_shape(P, s, &cur) && cur.M == first.M && cur.D == first.D &&
-          cur.Pd == first.Pd && cur.ldWl == first.ldWl && cur.ldWp == first.ldWp && cur.ldX == first.ldX && cur.ldA == last.ldC) {
-        run.push_back(s);
-        last = cur;
-        continue;
-      }
-      break;
-    }
-    for (int s : run) used[s] = 1;
-    if (run.size() > best.size()) { best = run; best_first = first; best_last = last; }
-  }
-  if (best.size() < 2) return false;
-  {
-    // the run's result must not land on its own input: blocks of rows start and finish at different times (a launch of
-    // more than one round of workgroups), so a block's result rows may only cover ITS OWN input rows - the same region
-    // with the same row stride - or nothing of the input at all
-    const int idIn = P.steps[best.front()].lhs, idOut = P.steps[best.back()].out;
-    const bool in_ws = idIn >= P.n_inputs, out_ws = idOut < P.n_inputs + P.n_steps - 1;
-    if (in_ws && out_ws) {
-      const int64_t es = P.elem_size();
-      const int64_t a0 = P.tensors[idIn].ws_offset, a1 = a0 + ((best_first.M - 1) * best_first.ldA + best_first.D) * es;
-      const int64_t b0 = P.tensors[idOut].ws_offset, b1 = b0 + ((best_first.M - 1) * best_last.ldC + best_first.D) * es;
-      const bool overlap = a0 < b1 && b0 < a1;
-      if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
-    }
-  }
-  d->on = true; d->steps = best;
-  d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
-  d->J = (int)((best_first.M + SWR - 1) / SWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
-  return true;
-}
-
-// Is k_sweep_f64 taken without CTN_SWEEP=1?  Decided by measurement.
-static constexpr bool kSweepF64Default = false;
-
-// The float64 plan keeps a site as TWO steps (plan.cpp fuses them for fp32 only): sa a GEMM of E[b, l] with a network
-// input W carrying {l, p, r}, sb the streaming step that sums p against a network input x[b, p].  Can k_sweep_f64 take
-// the pair as one site?  Matched on the tensors' labels, dims and strides: E and E' row-major [b][.], r unit-stride in W,
-// p unit-stride in x, every stride even (16-byte accesses).  The layout the planner gave C does not matter: C is never
-// written.
-struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
-static bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh) {
-  if (P.dtype != CTN_F64 || sb + 1 >= P.n_steps) return false;              // a step must follow the last member
-  const Step& a = P.steps[sa];
-  const Step& b = P.steps[sb];
-  if (a.kernel != CTN_KERNEL_MFMA_F64 || b.kernel != CTN_KERNEL_ELEMENT || a.rhs < 0 || b.rhs < 0 || a.lhs2 >= 0 || b.lhs2 >= 0 ||
-      a.epw || b.epw)
-    return false;
-  auto axis = [](const Tensor& t, int32_t lab) {
-    int found = -1;
-    for (size_t i = 0; i < t.labels.size(); ++i)
-      if (t.labels[i] == lab) { if (found >= 0) return -1; found = (int)i; }   // (a repeated label: no)
-    return found;
-  };
-  const int idW = P.tensors[a.lhs].labels.size() == 3 ? a.lhs : a.rhs, idE = idW == a.lhs ? a.rhs : a.lhs;
-  if (b.lhs != a.out && b.rhs != a.out) return false;
-  const int idX = b.lhs == a.out ? b.rhs : b.lhs;
-  if (idW >= P.n_inputs || idX >= P.n_inputs || idE == idW) return false;    // W, x: network inputs
-  const Tensor &tE = P.tensors[idE], &tW = P.tensors[idW], &tX = P.tensors[idX], &tC = P.tensors[a.out], &tO = P.tensors[b.out];
-  if (tE.labels.size() != 2 || tW.labels.size() != 3 || tX.labels.size() != 2 || tC.labels.size() != 3 || tO.labels.size() != 2) return false;
-  const int el = axis(tW, tE.labels[0]) >= 0 ? 0 : 1;                        // E = {b, l}: l is the label W carries
-  const int32_t ll = tE.labels[el], lb = tE.labels[1 - el];
-  if (ll == lb || axis(tW, ll) < 0 || axis(tW, lb) >= 0 || axis(tX, lb) < 0) return false;
-  const int32_t lp = tX.labels[1 - axis(tX, lb)];
-  if (lp == lb || lp == ll || axis(tW, lp) < 0) return false;
-  const int32_t lr = tW.labels[3 - axis(tW, ll) - axis(tW, lp)];
-  if (lr == ll || lr == lp || lr == lb) return false;
-  if (axis(tC, lb) < 0 || axis(tC, lp) < 0 || axis(tC, lr) < 0 || axis(tO, lb) < 0 || axis(tO, lr) < 0) return false;
-  const int64_t D = tE.dims[el], Pd = tW.dims[axis(tW, lp)], M = tE.dims[1 - el];
-  if ((D != 64 && D != 128 && D != 256 && D != 512) || (Pd != 2 && Pd != 4) || tW.dims[axis(tW, lr)] != D || M >= ((int64_t)1 << 31) - SWR)
-    return false;
-  if (tE.strides[el] != 1 || tW.strides[axis(tW, lr)] != 1 || tX.strides[axis(tX, lp)] != 1 || tO.strides[axis(tO, lr)] != 1) return false;
-  const int64_t ldA = tE.strides[1 - el], ldC = tO.strides[axis(tO, lb)], ldX = tX.strides[axis(tX, lb)];
-  const int64_t ldWl = tW.strides[axis(tW, ll)], ldWp = tW.strides[axis(tW, lp)];
-  if (ldA < D || ldC < D || ldX < Pd || ldWl <= 0 || ldWp <= 0 || ((ldA | ldC | ldX | ldWl | ldWp) & 1)) return false;
-  if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;   // a lane's offsets into a core: 32 bits, in bytes
-  sh->idE = idE; sh->idW = idW; sh->idX = idX; sh->idOut = b.out;
-  sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = (int)D; sh->Pd = (int)Pd;
-  return true;
-}
-
-// The longest run of such pairs, each taking the result of the one before as its E.  The two safety rules are those of
-// sweep_match: nothing that is launched may lie between two members, and the run's result may overlap its input only as
-// the same region with the same row stride.
-static bool sweep64_match(const Plan& P, Exec::SweepDesc* d) {
-  auto next_launched = [&](int s) { do ++s; while (s < P.n_steps && P.steps[s].kernel == CTN_KERNEL_FUSED); return s; };
-  std::vector<int> best;
-  std::vector<int32_t> best_ids;
-  Sweep64Site best_first, best_last;
-  std::vector<char> used((size_t)P.n_steps, 0);
-  for (int s0 = 0; s0 < P.n_steps; ++s0) {
-    Sweep64Site first, cur, last;
-    int sb = next_launched(s0);
-    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first)) continue;
-    std::vector<int> run{s0, sb};
-    std::vector<int32_t> ids{first.idW, first.idX};
-    last = first;
-    for (;;) {
-      const int na = next_launched(run.back());
-      const int nb = na < P.n_steps ? next_launched(na) : na;
-      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
-          cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC)
-        break;
-      run.push_back(na); run.push_back(nb);
-      ids.push_back(cur.idW); ids.push_back(cur.idX);
-      last = cur;
-    }
-    for (int s : run) used[s] = 1;
-    if (run.size() > best.size()) { best = run; best_ids = ids; best_first = first; best_last = last; }
-  }
-  if (best.size() < 4) return false;            // at least 2 sites
-  {
-    const int idIn = best_first.idE, idOut = best_last.idOut;
-    const bool in_ws = idIn >= P.n_inputs, out_ws = idOut < P.n_inputs + P.n_steps - 1;
-    if (in_ws && out_ws) {
-      const int64_t es = P.elem_size();
-      const int64_t a0 = P.tensors[idIn].ws_offset, a1 = a0 + ((best_first.M - 1) * best_first.ldA + best_first.D) * es;
-      const int64_t b0 = P.tensors[idOut].ws_offset, b1 = b0 + ((best_first.M - 1) * best_last.ldC + best_first.D) * es;
-      const bool overlap = a0 < b1 && b0 < a1;
-      if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
-    }
-  }
-  d->on = true; d->f64 = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
-  d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
-  d->J = (int)((best_first.M + SWR - 1) / SWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
-  return true;
-}
-
-// Is this split dot step the sum over k = (a, b) of X[a Kb + b] Y[b ldY + a] - one operand contiguous in k, the other
-// one its transpose (k_dot_tr)?  Checked on the plan's k tables.
-static bool dot_tr_match(const Plan& P, const Step& st, Exec::DotTr* d) {
-  if (st.kernel != CTN_KERNEL_DOT || st.K < 32768 || st.K >= (1LL << 31)) return false;
-  const int32_t* T = P.tables.data();
-  for (int x_is_a = 1; x_is_a >= 0; --x_is_a) {
-    const int32_t* kx = T + (x_is_a ? st.t.okA : st.t.okB);
-    const int32_t* ky = T + (x_is_a ? st.t.okB : st.t.okA);
-    bool contig = true;
-    for (int64_t k = 0; k < st.K && contig; ++k) contig = kx[k] == k;
-    if (!contig || ky[0] != 0) continue;
-    const int64_t ldY = ky[1];
-    if (ldY < 32) continue;
-    int64_t Kb = 0;
-    for (int64_t k = 1; k < st.K; ++k) if (ky[k] == 1) { Kb = k; break; }
-    if (Kb < 32 || st.K % Kb != 0) continue;
-    const int64_t Ka = st.K / Kb;
-    if (Ka % 32 != 0 || Kb % 32 != 0 || ldY < Ka) continue;
-    bool ok = true;
-    for (int64_t k = 0; k < st.K && ok; ++k) ok = ky[k] == (k % Kb) * ldY + k / Kb;
-    if (!ok) continue;
-    d->on = true; d->Ka = (int)Ka; d->Kb = (int)Kb; d->x_is_a = x_is_a; d->ldY = ldY;
-    return true;
-  }
-  return false;
-}
-
-// Can step s run on k_mfma_f32_ares, and how many 128-column tiles should a workgroup walk?  Checked on the plan's own
-// tables (0 = no): M = K = 256, N a multiple of 128, B vector-loadable along n or along k, every
-// 128-column tile of C dense, more workgroup partials than slots (the step already goes through k_collapse), and
-// enough tiles that workgroups of at least four fill the chip's last round.
-static int ares_match(const Plan& P, int s, int R, int n_cu, const DevSwitches& sw) {
-  const Step& st = P.steps[s];
-  if (sw.ares == 0 || P.dtype != CTN_F32 || st.kernel != CTN_KERNEL_MFMA_F32 || st.rhs < 0 || st.lhs2 >= 0 || st.epw ||
-      st.M != AR_M || st.K != AR_K || st.N % AR_TN != 0 || !st.collapse)
-    return 0;
-  if (st.modeB != 1 && st.modeB != 2) return 0;
-  const int32_t* T = P.tables.data();
-  const int32_t *onB = T + st.t.onB, *okB = T + st.t.okB, *onC = T + st.t.onC;
-  for (int64_t n = 0; n < st.N; ++n)
-    if (onC[n] != onC[n & ~(int64_t)(AR_TN - 1)] + (n & (AR_TN - 1))) return 0;
-  if (st.modeB == 1) {
-    for (int64_t n = 0; n < st.N; n += 4)
-      if (onB[n + 1] != onB[n] + 1 || onB[n + 2] != onB[n] + 2 || onB[n + 3] != onB[n] + 3 || onB[n] % 4) return 0;
-  } else {
-    for (int k = 0; k < AR_K; k += 4)
-      if (okB[k + 1] != okB[k] + 1 || okB[k + 2] != okB[k] + 2 || okB[k + 3] != okB[k] + 3 || okB[k] % 4) return 0;
-    for (int64_t n = 0; n < st.N; ++n) if (onB[n] % 4) return 0;
-  }
-  const int64_t tiles = st.N / AR_TN;       // per batch entry: a workgroup's tiles are tiles of one matrix
-  R *= (int)st.Bt;
-  if (sw.ares != 1 && tiles * 2 * R < 2LL * n_cu) return 0;         // (the throughput regime of the large-tile kernel)
-  if (sw.ares_ntw > 0) return tiles % sw.ares_ntw == 0 ? sw.ares_ntw : 0;
-  // as many tiles per workgroup as still fill the last round of workgroups (a workgroup's load of A costs about a
-  // quarter of a tile), at least 4
-  for (int ntw : {64, 32, 16, 8, 4}) {
-    if (tiles % ntw) continue;
-    const int64_t wgs = tiles / ntw * R, rounds = (wgs + n_cu - 1) / n_cu;
-    if (wgs * 100 >= rounds * n_cu * 94) return ntw;
-  }
-  return sw.ares == 1 && tiles % 4 == 0 ? 4 : 0;
-}
-
-// ... and can the resident operand be fetched with 16-byte loads along k?
-static bool ares_avec(const Plan& P, int s) {
-  const Step& st = P.steps[s];
-  if (st.modeA != 2) return false;
-  const int32_t* T = P.tables.data();
-  const int32_t *omA = T + st.t.omA, *okA = T + st.t.okA, *obA = T + st.t.obA;
-  if (obA[0] % 4 || P.tensors[st.lhs].numel % 4) return false;
-  for (int k = 0; k < AR_K; ++k) if (okA[k] != okA[0] + k) return false;
-  if (okA[0] % 4) return false;
-  for (int m = 0; m < AR_M; ++m) if (omA[m] % 4) return false;
-  return true;
-}
 
 // ---------------------------------------------------------------------------
 // the launch path: exec_launch_steps walks the plan and hands every step to the launch_<form> of its form.  Its helpers
@@ -758,7 +369,7 @@ static int mark_absorbed(Exec* E, int s) {
 static void report_tile(Exec* E, int s, int tm, int tn) { E->launched_tile[s] = (tm << 16) | tn; }
 
 // step s's region of the partial sums, and its slots per replica
-static double* part_region(Exec* E, int s) { return E->d_partials + (size_t)E->step_off[s] * E->R; }
+static double* part_region(Exec* E, int s) { return E->d_partials + (size_t)E->forms.step_off[s] * E->R; }
 
 // The partials of tensor `id`'s producer - unless the tensor is a network input (or absent), carries scale 1 (eager
 // mode: normalised in place), or was never written (CTN_KERNEL_FUSED)
@@ -768,7 +379,7 @@ static void producer_partials(Exec* E, int id, const double** p, int32_t* cnt, i
   if (id >= P.n_inputs && P.stabilize && !E->eager_rescale && P.steps[P.tensors[id].producer].kernel != CTN_KERNEL_FUSED) {
     const int ps = P.tensors[id].producer;
     *p = part_region(E, ps);
-    *cnt = *stride = E->step_partials[ps];
+    *cnt = *stride = E->forms.step_partials[ps];
     *numel = (double)P.tensors[id].numel;
   }
 }
@@ -809,7 +420,7 @@ static void fill_step_args(Exec* E, int s, StepArgs* args) {
   a.epw = st.epw | (st.epw_split ? 0x100 : 0);
   // more workgroup partials than slots: through the scratch buffer and k_collapse
   a.partC = st.collapse ? E->d_scratch : part_region(E, s);
-  a.partC_stride = st.collapse ? st.blocks : E->step_partials[s];
+  a.partC_stride = st.collapse ? st.blocks : E->forms.step_partials[s];
   a.min_norm = P.min_norm;
   a.Bt = (int32_t)st.Bt; a.M = (int32_t)st.M; a.N = (int32_t)st.N; a.K = (int32_t)st.K;
   a.idA = st.lhs; a.idB = st.rhs >= 0 ? st.rhs : E->n_tensors - 1; a.idC = st.out;
@@ -853,7 +464,7 @@ static int launch_chain(Exec* E) {
 }
 
 // a group of leaf steps whose arguments are in device memory
-static void launch_group(Exec* E, const Exec::LeafGroup& G) {
+static void launch_group(Exec* E, const LeafGroup& G) {
   const dim3 g(G.blocks, E->R, G.len);
   if (E->plan->dtype == CTN_F32) launch_stream_group<float>(G.vw, G.u, g, E->stream, E->d_group_args + G.off);
   else launch_stream_group<double>(G.vw, G.u, g, E->stream, E->d_group_args + G.off);
@@ -864,7 +475,7 @@ static int launch_sweep64(Exec* E, int s) {
   const Plan& P = *E->plan;
   const Step& st = P.steps[s];
   const int R = E->R;
-  const Exec::SweepDesc& sd = E->sweep;
+  const SweepDesc& sd = E->forms.sweep;
   const int S = (int)sd.steps.size() / 2;
   Sweep64Args w{};
   w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
@@ -904,7 +515,7 @@ static int launch_sweep(Exec* E, int s) {
   const Plan& P = *E->plan;
   const Step& st = P.steps[s];
   const int R = E->R;
-  const Exec::SweepDesc& sd = E->sweep;
+  const SweepDesc& sd = E->forms.sweep;
   const int S = (int)sd.steps.size();
   const Step& f0 = P.steps[sd.steps.front()];
   SweepArgs w{};
@@ -946,10 +557,10 @@ static int launch_sweep(Exec* E, int s) {
 
 // a step of a sweep: the members before the last launch nothing, the last one launches the run
 static int launch_sweep_member(Exec* E, int s) {
-  if (E->sweep_role[s] == 1) return mark_absorbed(E, s);
+  if (E->forms.sweep_role[s] == 1) return mark_absorbed(E, s);
   const StepTimer t(E, s);
   if (t.rc != CTN_OK) return t.rc;
-  const int rc = E->sweep.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
+  const int rc = E->forms.sweep.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
   return rc != CTN_OK ? rc : t.end();
 }
 
@@ -958,8 +569,8 @@ static int launch_zip_lat(Exec* E, int s) {
   const Plan& P = *E->plan;
   const Step& st = P.steps[s];
   const int R = E->R;
-  const Exec::ZipLat& L = E->zl[s];
-  const Exec::ZipDesc& zd = L.d;
+  const ZipLat& L = E->forms.zl[s];
+  const ZipDesc& zd = L.d;
   const Step& s1 = P.steps[s - 1];
   const int S = ZM / L.mp, nub = zd.U / 16;
   const bool eager = E->eager_rescale;
@@ -973,7 +584,7 @@ static int launch_zip_lat(Exec* E, int s) {
   producer_partials(E, s1.lhs, &z.partE, &z.PE, &z.strideE, &z.numelE);
   z.min_norm = P.min_norm;
   z.partC = part_region(E, s);
-  z.partC_stride = E->step_partials[s];
+  z.partC_stride = E->forms.step_partials[s];
   const StepTimer t(E, s);
   if (t.rc != CTN_OK) return t.rc;
   report_tile(E, s, L.mp, ZM);      // (m1 part, all n2) per workgroup, 16 values of u
@@ -985,7 +596,7 @@ static int launch_zip_lat(Exec* E, int s) {
   else if (zd.Q == 4) hipLaunchKernelGGL((k_zip_lat<4, 64>), gz, dim3(512), 0, E->stream, z);
   else hipLaunchKernelGGL((k_zip_lat<2, 64>), gz, dim3(512), 0, E->stream, z);
   if (!L.feeds_next || eager) {                 // nobody adds these slabs up while loading them: do it here
-    hipLaunchKernelGGL(k_zip_slab_sum, dim3((unsigned)E->step_partials[s], (unsigned)R), dim3(256), 0, E->stream,
+    hipLaunchKernelGGL(k_zip_slab_sum, dim3((unsigned)E->forms.step_partials[s], (unsigned)R), dim3(256), 0, E->stream,
                        (const float*)z.slabs_out, S, zd.U, (void* const*)E->d_ptrs, E->n_tensors, st.out, zd.ldC, z.partC,
                        z.partC_stride);
     launch_renorm(E, s);
@@ -1003,10 +614,10 @@ static void launch_renorm(Exec* E, int s) {
   const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((numel / V + 255) / 256, 2048)), E->R);
   if (P.dtype == CTN_F32)
     hipLaunchKernelGGL(k_renorm<float>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, out, numel,
-                       (const double*)part_region(E, s), E->step_partials[s], E->step_partials[s], P.min_norm);
+                       (const double*)part_region(E, s), E->forms.step_partials[s], E->forms.step_partials[s], P.min_norm);
   else
     hipLaunchKernelGGL(k_renorm<double>, g, dim3(256), 0, E->stream, (void* const*)E->d_ptrs, E->n_tensors, out, numel,
-                       (const double*)part_region(E, s), E->step_partials[s], E->step_partials[s], P.min_norm);
+                       (const double*)part_region(E, s), E->forms.step_partials[s], E->forms.step_partials[s], P.min_norm);
 }
 
 // The zipper-pair kernels by ctn_step_form: threads per workgroup, the tile ctn_exec_step_tile reports, and whether a
@@ -1034,7 +645,7 @@ static int launch_zip(Exec* E, int s) {
   const Plan& P = *E->plan;
   const Step& st = P.steps[s];
   const int R = E->R;
-  const Exec::ZipDesc& zd = E->zip[s];
+  const ZipDesc& zd = E->forms.zip[s];
   const ZipKernel& zk = kZipKernels[zd.form];
   const Step& s1 = P.steps[s - 1];
   ZipArgs z{};
@@ -1045,7 +656,7 @@ static int launch_zip(Exec* E, int s) {
   producer_partials(E, s1.lhs, &z.partE, &z.PE, &z.strideE, &z.numelE);
   z.min_norm = P.min_norm;
   z.partC = part_region(E, s);
-  z.partC_stride = E->step_partials[s];
+  z.partC_stride = E->forms.step_partials[s];
   z.R = R; z.dbg = nullptr;
   z.n_items = (int32_t)zipq_items(R, zd.U, zd.zu);
   const StepTimer t(E, s);
@@ -1069,7 +680,7 @@ struct Collapse { bool on; int blocks; };
 static int launch_cplx(Exec* E, int s, Collapse* col) {
   const Plan& P = *E->plan;
   const int R = E->R;
-  const CplxDesc& cd = E->cplx[s];
+  const CplxDesc& cd = E->forms.cplx[s];
   const int32_t* CT = E->d_cplx_tabs;
   CplxArgs c{};
   c.txr = CT + cd.txr; c.txk = CT + cd.txk; c.tyn = CT + cd.tyn; c.tyk = CT + cd.tyk; c.tcx = CT + cd.tcx; c.tcy = CT + cd.tcy;
@@ -1086,7 +697,7 @@ static int launch_cplx(Exec* E, int s, Collapse* col) {
   col->on = c.blocks_per_replica > kMaxPartials;       // more workgroups than slots: through the collapse pass
   col->blocks = c.blocks_per_replica;
   c.partC = col->on ? E->d_scratch : part_region(E, s);
-  c.partC_stride = col->on ? col->blocks : E->step_partials[s];
+  c.partC_stride = col->on ? col->blocks : E->forms.step_partials[s];
   report_tile(E, s, CX_TX, 2 * CX_TY);   // 64 pairs of `small` x (128 entries of `big` x 2 components): no plain form reports it
   const dim3 gc((unsigned)((int64_t)c.blocks_per_replica * R));
   if (cd.kfx && cd.kfy) hipLaunchKernelGGL((k_cmfma_f32<true, true>), gc, dim3(256), 0, E->stream, c);
@@ -1151,7 +762,7 @@ static int launch_gsplitk(Exec* E, int s, StepArgs& a, const StepForm& f) {
   a.ks_slab = sk.slab; a.ks_numelC = sk.numelC; a.ks_S = sk.S; a.ks_chunk = sk.kchunk;
   launch_g_tiles(E, st, a, !E->sw.g_no_asm);           // (every split is whole k-tiles)
   a.ks_slab = nullptr; a.ks_S = 0;
-  launch_splitk_reduce<float>(E, E->step_partials[s], E->R, a, sk);
+  launch_splitk_reduce<float>(E, E->forms.step_partials[s], E->R, a, sk);
   return CTN_OK;
 }
 
@@ -1206,8 +817,8 @@ static int launch_lat64(Exec* E, int s, StepArgs& a, const StepForm& f) {
 
 // the reduce pass of a K split over workgroups, in the plan's precision
 static void launch_reduce(Exec* E, int s, StepArgs& a, const SplitKArgs& sk) {
-  if (E->plan->dtype == CTN_F32) launch_splitk_reduce<float>(E, E->step_partials[s], E->R, a, sk);
-  else launch_splitk_reduce<double>(E, E->step_partials[s], E->R, a, sk);
+  if (E->plan->dtype == CTN_F32) launch_splitk_reduce<float>(E, E->forms.step_partials[s], E->R, a, sk);
+  else launch_splitk_reduce<double>(E, E->forms.step_partials[s], E->R, a, sk);
 }
 
 // the latency mode of either precision: 64 x 64 tiles, K split over workgroups
@@ -1252,7 +863,7 @@ static int launch_dot(Exec* E, int s, StepArgs& a, const StepForm& f) {
   if (f.kind == Kind::DotSplit) {
     const SplitKArgs sk = slab_args(E, s, f);
     const dim3 g((unsigned)f.blocks, R);
-    const Exec::DotTr dt = (int)E->dot_tr.size() == P.n_steps ? E->dot_tr[s] : Exec::DotTr();
+    const DotTr& dt = E->forms.dot_tr[s];
     if (P.dtype == CTN_F32) {
       if (dt.on) hipLaunchKernelGGL(k_dot_tr<float>, g, dim3(256), 0, E->stream, a, (float*)sk.slab, sk.numelC, sk.S, dt.Ka, dt.Kb, dt.ldY, dt.x_is_a);
       else hipLaunchKernelGGL(k_dot_split<float>, g, dim3(256), 0, E->stream, a, (float*)sk.slab, sk.numelC, sk.S, sk.kchunk);
@@ -1281,7 +892,7 @@ static SplitKArgs split_stream_args(Exec* E, int s, StepArgs& a, const StepForm&
 // ... and the reduce pass writes the step's region itself
 static void reduce_split_stream(Exec* E, int s, StepArgs& a, const StepForm& f, const SplitKArgs& sk) {
   if (!f.S) return;
-  a.partC = part_region(E, s); a.partC_stride = E->step_partials[s];
+  a.partC = part_region(E, s); a.partC_stride = E->forms.step_partials[s];
   launch_reduce(E, s, a, sk);
 }
 
@@ -1314,7 +925,7 @@ static int launch_stream(Exec* E, int s, StepArgs& a, const StepForm& f, GroupCo
   stream_variant(st, E->R, vw, &u, &nq);
   a.dNq = make_fastdiv(nq / u);
   if (gc->left > 0) {
-    Exec::LeafGroup& G = E->groups[gc->head];
+    LeafGroup& G = E->forms.groups[gc->head];
     E->h_group_args[G.off + (s - gc->head)] = a;
     if (--gc->left == 0) {
       HIPCHECK(hipMemcpyAsync(E->d_group_args + G.off, E->h_group_args + G.off, sizeof(StepArgs) * G.len,
@@ -1352,9 +963,9 @@ static int launch_step(Exec* E, int s, GroupCollect* gc) {
   if ((f32 || st.kernel == CTN_KERNEL_MFMA_F64) && (int64_t)st.blocks * E->R >= (1LL << 31)) { g_err = "grid too large"; return CTN_UNSUPPORTED; }
   Collapse col{st.collapse, st.blocks};
   int rc = CTN_OK;
-  if (f32 && !E->cplx.empty() && E->cplx[s].on) {
+  if (f32 && E->forms.role[s] == Role::Cplx) {
     rc = launch_cplx(E, s, &col);
-  } else if (const int ntw_av = f32 && (int)E->ares_ntw.size() == P.n_steps ? E->ares_ntw[s] : 0) {
+  } else if (const int ntw_av = f32 ? E->forms.ares_ntw[s] : 0) {
     rc = launch_ares(E, s, a, ntw_av, &col);
   } else {
     const StepForm f = step_form(P, s, E->R, E->n_cu, E->sw, a.c_vec != 0);
@@ -1367,7 +978,7 @@ static int launch_step(Exec* E, int s, GroupCollect* gc) {
         a.blocks_per_replica = (int32_t)f.blocks;
       }
       a.partC = f.collapse ? E->d_scratch : part_region(E, s);
-      a.partC_stride = f.collapse ? (int32_t)f.collapse_blocks : E->step_partials[s];
+      a.partC_stride = f.collapse ? (int32_t)f.collapse_blocks : E->forms.step_partials[s];
     }
     switch (f.kind) {
       case Kind::None: break;                                              // (CTN_KERNEL_FUSED never gets here)
@@ -1427,9 +1038,9 @@ static int exec_launch_steps(Exec* E) {
     GroupCollect gc;
     for (int s = 0; s < P.n_steps && rc == CTN_OK; ++s) {
       if (group_skip > 0) { --group_skip; continue; }   // went out with the head of its group
-      if (gc.left == 0 && !E->groups.empty() && E->groups[s].len >= 2 && E->sw.group && !E->eager_rescale &&
+      if (gc.left == 0 && E->forms.groups[s].len >= 2 && E->sw.group && !E->eager_rescale &&
           !(E->timing_runs < E->timing_slots)) {
-        const Exec::LeafGroup& G = E->groups[s];
+        const LeafGroup& G = E->forms.groups[s];
         if (G.ready) {
           launch_group(E, G);
           group_skip = G.len - 1;
@@ -1437,14 +1048,16 @@ static int exec_launch_steps(Exec* E) {
         }
         gc.left = G.len; gc.head = s;   // first time: the steps' arguments are built by launch_stream, not launched
       }
-      if (!E->sweep_role.empty() && E->sweep_role[s] && !E->eager_rescale) rc = launch_sweep_member(E, s);
-      else if (!E->zl_skip.empty() && E->zl_skip[s]) rc = mark_absorbed(E, s);   // first step of a pair in its latency form
-      else if (!E->zl.empty() && E->zl[s].on) rc = launch_zip_lat(E, s);
-      else if (!E->zip_skip.empty() && E->zip_skip[s]) rc = mark_absorbed(E, s); // first step of a zipper pair
-      else if (!E->zip.empty() && E->zip[s].on) rc = launch_zip(E, s);
-      else if (!E->cplx_skip.empty() && E->cplx_skip[s]) rc = mark_absorbed(E, s);   // the S step of a complex pair
-      else if (P.steps[s].kernel == CTN_KERNEL_FUSED) rc = time_nothing(E, s);   // formed on the fly inside its consumer
-      else rc = launch_step(E, s, &gc);
+      if (E->forms.sweep_role[s] && !E->eager_rescale) { rc = launch_sweep_member(E, s); continue; }
+      switch (E->forms.role[s]) {
+        case Role::ZipLat: rc = launch_zip_lat(E, s); break;
+        case Role::Zip: rc = launch_zip(E, s); break;
+        case Role::Absorbed: rc = mark_absorbed(E, s); break;   // first step of a zipper pair, S step of a complex pair
+        case Role::Cplx: case Role::Plain:                      // (launch_step reads the role again)
+          if (P.steps[s].kernel == CTN_KERNEL_FUSED) rc = time_nothing(E, s);   // formed on the fly inside its consumer
+          else rc = launch_step(E, s, &gc);
+          break;
+      }
     }
   }
   if (rc != CTN_OK) return rc;
@@ -1662,7 +1275,17 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   E.launched_tile.assign(P.n_steps, 0);
   E.launched_form.assign(P.n_steps, 0);
   E.n_tensors = P.n_inputs + P.n_steps + 1;
+  // every decision first (host code, fused_forms.h); what follows allocates and uploads what the record asks for
+  E.forms = fused_forms(P, replicas, E.n_cu, E.sw);
+  const FusedForms& F = E.forms;
   auto fail = [&](int code) { delete x; return code; };
+  // `bytes` of device memory (none: the pointer stays null) ... filled with a host vector
+  auto dev_alloc = [](auto** d, size_t bytes) { return bytes ? hipMalloc((void**)d, bytes) : hipSuccess; };
+  auto dev_upload = [&](auto** d, const auto& h) {
+    const size_t bytes = h.size() * sizeof(h[0]);
+    const hipError_t e = dev_alloc(d, bytes);
+    return e != hipSuccess || !bytes ? e : hipMemcpy(*d, h.data(), bytes, hipMemcpyHostToDevice);
+  };
 #define HIPCHECK_X(expr)                                                        \
   do {                                                                          \
     hipError_t e_ = (expr);                                                     \
@@ -1680,305 +1303,26 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   HIPCHECK_X(hipMalloc((void**)&E.d_tables64, std::max<size_t>(P.tables64.size(), 2) * 8));
   HIPCHECK_X(hipMemcpy(E.d_tables64, P.tables64.data(), P.tables64.size() * 8, hipMemcpyHostToDevice));
   HIPCHECK_X(hipMalloc((void**)&E.d_ptrs, (size_t)replicas * E.n_tensors * sizeof(void*)));
-  {
-    size_t slab_elems = 0;   // split-K scratch: S slabs shaped like the step's output, per replica
-    // the splits the launcher will take: it asks step_form too, and the answer does not depend on the caller's buffers
-    auto splits_of = [&](int s) { return step_form(P, s, replicas, E.n_cu, E.sw, P.steps[s].cvec).S; };
-    for (int s = 0; s < P.n_steps; ++s)
-      if (const int S = splits_of(s))
-        slab_elems = std::max(slab_elems, (size_t)S * (size_t)P.tensors[P.steps[s].out].numel * (size_t)replicas);
-    if (slab_elems) HIPCHECK_X(hipMalloc((void**)&E.d_slab, slab_elems * (P.dtype == CTN_F64 ? 8 : 4)));
-    size_t fold_elems = 0;   // a step with more than 16 slabs folds them 16 to 1 into this buffer and back
-    for (int s = 0; s < P.n_steps; ++s)
-      if (const int S = splits_of(s))
-        if (S > 16)
-          fold_elems = std::max(fold_elems, (size_t)((S + 15) / 16) * (size_t)P.tensors[P.steps[s].out].numel * (size_t)replicas);
-    if (fold_elems) HIPCHECK_X(hipMalloc((void**)&E.d_slab2, fold_elems * (P.dtype == CTN_F64 ? 8 : 4)));
-  }
-  // partial counts: plan value, one per tile in the latency form, and the split-K reduce pass spreads over up to
-  // 64 workgroups per replica; every step gets a region of exactly that many slots per replica
-  E.step_partials.resize(P.n_steps);
-  E.step_off.resize(P.n_steps);
-  int64_t scratch_need = std::max<int64_t>(P.max_collapse_blocks, 1);
-  for (int s = 0; s < P.n_steps; ++s) {
-    const Step& st = P.steps[s];
-    E.step_partials[s] = std::max(st.partials, 1);
-    if (P.chain) { E.step_off[s] = E.part_slots++; continue; }   // the chain walker: one slot per step, whatever the kernel kind
-    // (a step with S > 0 has made d_slab non-null just above, and the launcher drops no split for want of it)
-    const StepForm f = step_form(P, s, replicas, E.n_cu, E.sw, st.cvec);
-    E.step_partials[s] = f.partials;
-    scratch_need = std::max<int64_t>(scratch_need, f.collapse_blocks);
-    E.step_off[s] = E.part_slots;
-    E.part_slots += E.step_partials[s];
-  }
-  // zipper pairs: at least one full round of workgroups (each is 134 MFLOP long), or CTN_ZIP=1
-  if (!P.chain && E.sw.zip != 0) {
-    E.zip.assign(P.n_steps, Exec::ZipDesc());
-    E.zip_skip.assign(P.n_steps, 0);
-    bool any = false;
-    for (int s = 1; s + 1 < P.n_steps; ++s) {
-      Exec::ZipDesc z;
-      if (E.zip_skip[s - 1] || (s >= 2 && E.zip[s - 1].on)) continue;
-      // 128 values of u per workgroup (k_zip_f32) when that fills the chip - or CTN_ZIP=1; else 64 (k_zip64_f32) when THAT
-      // does: 64 ... 127 networks of |u| = 256 - or CTN_ZIP=2; fewer networks keep the two-launch / latency forms
-      // ... and of the two the one whose workgroups fill their rounds better (one workgroup per CU and round: 96 networks
-      // are 192 workgroups of 128 - refused - or 384 of 64 - a round and a half: 26.0 ms against 23.0 on the two-launch
-      // forms - while 64 networks are exactly one round of 64: 13.5 ms against 15.9)
-      auto fill = [&](int64_t wgs) { return (double)wgs / (double)(((wgs + E.n_cu - 1) / E.n_cu) * E.n_cu); };
-      Exec::ZipDesc z128, z64;
-      if (P.dtype == CTN_F64) {
-        // fp64: one form, 64 values of u per workgroup (k_zip_f64), and only on request (CTN_ZIP=1).  kZipF64Default is
-        // where the rule of the fp32 forms - at least one round of workgroups, rounds filled to 0.9 - would switch it on
-        // unasked; the measurement that has to decide that is in DESIGN section 10.
-        if (E.sw.zip == 2 || !zip_match(P, s, &z, CTN_F64, ZDU)) continue;
-        const int64_t wgs = (int64_t)(z.U / ZDU) * replicas;
-        if (E.sw.zip != 1 && !(kZipF64Default && wgs >= E.n_cu && fill(wgs) >= 0.9)) continue;
-        if (z.U / ZDU > kMaxPartials) continue;
-        z.zu = ZDU; z.form = CTN_FORM_ZIP_F64;
-        E.zip[s] = z;
-        E.zip_skip[s - 1] = 1;
-        any = true;
-        E.part_slots -= E.step_partials[s];
-        E.step_partials[s] = z.U / z.zu;
-        E.part_slots += E.step_partials[s];
-        continue;
-      }
-      const bool m128 = E.sw.zip != 2 && zip_match(P, s, &z128, CTN_F32) && (E.sw.zip == 1 || (int64_t)(z128.U / ZU) * replicas >= E.n_cu);
-      const bool m64 = E.sw.zip != 1 && zip_match(P, s, &z64, CTN_F32, Z6U) && z64.K1 % Z6K == 0 &&
-                       (E.sw.zip == 2 || (int64_t)(z64.U / Z6U) * replicas >= E.n_cu);
-      const double f128 = m128 ? fill((int64_t)(z128.U / ZU) * replicas) : 0.0, f64 = m64 ? fill((int64_t)(z64.U / Z6U) * replicas) : 0.0;
-      bool ok = false;
-      if (m128 && (E.sw.zip == 1 || f128 >= 0.9 || f128 >= f64)) { ok = true; z = z128; z.zu = ZU; z.form = CTN_FORM_ZIP; }
-      else if (m64 && (E.sw.zip == 2 || f64 >= 0.9)) { ok = true; z = z64; z.zu = Z6U; z.form = CTN_FORM_ZIP64; }
-      else if (m128) { ok = true; z = z128; z.zu = ZU; z.form = CTN_FORM_ZIP; }
-      // the 128-u form with two legs per pass (k_zipq_f32): on request wherever the pair matches (CTN_ZIPQ=1, also where
-      // the rules above chose otherwise - but not against CTN_ZIP=2), else under k_zip_f32's own default rule
-      // ... and its walking form (k_zipqp_f32): on request (CTN_ZIPQ=2) wherever CTN_ZIPQ=1 takes k_zipq_f32, else under
-      // kZipQPDefault where that kernel is taken by default and has two rounds of workgroups at least
-      if ((E.sw.zipq == 1 || E.sw.zipq == 2) && E.sw.zip != 2 && zip_match(P, s, &z128, CTN_F32) && zipq_fits(z128)) {
-        ok = true; z = z128; z.zu = ZU; z.zq = true; z.zqp = E.sw.zipq == 2;
-        z.form = z.zqp ? CTN_FORM_ZIPQP : CTN_FORM_ZIPQ;
-      } else if (E.sw.zipq == -1 && kZipQDefault && E.sw.zip == -1 && ok && z.zu == ZU && f128 >= 0.9 && zipq_fits(z)) {
-        z.zq = true;
-        z.zqp = kZipQPDefault && zipq_items(replicas, z.U, ZU) >= 2 * (int64_t)E.n_cu;
-        z.form = z.zqp ? CTN_FORM_ZIPQP : CTN_FORM_ZIPQ;
-      }
-      // bond 128 (k_zip128_f32: 128 values of u per workgroup, K1 a multiple of its tile depth and two tiles at least -
-      // ZK = Z1K, as zip_match checks), when no bond-256 form matches: only on request (CTN_ZIP=1, and not CTN_ZIP128=0).
-      // kZip128Default is where the rule of the other forms - at least one round of workgroups, rounds filled to 0.9 - would switch it on unasked;
-      // the measurement that has to decide that is in DESIGN section 10.
-      static_assert(Z1K == ZK, "zip_match checks K1 against ZK; k_zip128_f32's tile depth must be the same");
-      if (!m128 && !m64 && E.sw.zip128 != 0 && E.sw.zip != 0 && E.sw.zip != 2 && zip_match(P, s, &z, CTN_F32, Z1U, Z1M) &&
-          z.K1 % Z1K == 0 && z.K1 >= 2 * Z1K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
-          (E.sw.zip == 1 || (kZip128Default && (int64_t)(z.U / Z1U) * replicas >= E.n_cu && fill((int64_t)(z.U / Z1U) * replicas) >= 0.9))) {
-        ok = true; z.zu = Z1U; z.zm = Z1M; z.form = CTN_FORM_ZIP128;
-      }
-      // bond 64 (k_zipm64_f32: 64 values of u per workgroup, the same tile depth), when neither a bond-256 nor the bond-128
-      // form matches: only on request (CTN_ZIP=1, and not CTN_ZIPM64=0).  kZipM64Default as kZip128Default: the
-      // measurement that has to decide it is in DESIGN section 10.
-      static_assert(Z4K == ZK, "zip_match checks K1 against ZK; k_zipm64_f32's tile depth must be the same");
-      if (!ok && E.sw.zipm64 != 0 && E.sw.zip != 0 && E.sw.zip != 2 && zip_match(P, s, &z, CTN_F32, Z4U, Z4M) &&
-          z.K1 % Z4K == 0 && z.K1 >= 2 * Z4K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
-          (E.sw.zip == 1 || (kZipM64Default && (int64_t)(z.U / Z4U) * replicas >= E.n_cu && fill((int64_t)(z.U / Z4U) * replicas) >= 0.9))) {
-        ok = true; z.zu = Z4U; z.zm = Z4M; z.form = CTN_FORM_ZIPM64;
-      }
-      if (!ok || z.U / z.zu > kMaxPartials) continue;    // (one abs-sum partial per workgroup: the consumers add at most that many)
-      E.zip[s] = z;
-      E.zip_skip[s - 1] = 1;
-      any = true;
-      // one abs-sum partial per workgroup of the fused launch; the skipped step keeps its (never written, zero) slots
-      E.part_slots -= E.step_partials[s];
-      E.step_partials[s] = z.U / z.zu;
-      E.part_slots += E.step_partials[s];
-    }
-    if (any) {   // regions moved: lay the offsets out again
-      E.part_slots = 0;
-      for (int s = 0; s < P.n_steps; ++s) { E.step_off[s] = E.part_slots; E.part_slots += E.step_partials[s]; }
-    } else {
-      E.zip.clear(); E.zip_skip.clear();
-    }
-  }
-  // the same pairs in their latency form: a few networks in flight (or CTN_ZIPL=1), and no throughput-form pair taken
-  if (!P.chain && P.dtype == CTN_F32 && E.zip.empty() && E.sw.zipl != 0 && (E.sw.zipl == 1 || replicas <= E.sw.zipl_max_r)) {
-    E.zl.assign(P.n_steps, Exec::ZipLat());
-    E.zl_skip.assign(P.n_steps, 0);
-    bool any = false;
-    int64_t slab_elems = 0;
-    for (int s = 1; s + 1 < P.n_steps; ++s) {
-      Exec::ZipDesc z;
-      if (E.zl_skip[s - 1] || (s >= 2 && E.zl[s - 1].on) || !zip_match(P, s, &z, CTN_F32, 16)) continue;
-      if (z.K1 != ZM || (z.Q != 4 && z.Q != 2) || z.ldC % 4 || z.ldE % 4 || z.ldXk % 4 || z.ldXq % 4 || z.ldYm % 4 || z.ldYq % 4) continue;
-      // the part of m1 a workgroup owns: 32 (8 slabs, 128 workgroups per network at |u| = 256) while that still fits ONE
-      // round of workgroups, else 64 (4 slabs, half the workgroups, each with twice the work per byte it loads)
-      int mp = 64;
-      if (z.Q == 4 && (E.sw.zipl_mp == 32 || (E.sw.zipl_mp == 0 && (int64_t)replicas * (z.U / 16) * 8 <= E.n_cu))) mp = 32;
-      const int S = ZM / mp;
-      if ((z.U / 16) * S > kMaxPartials) continue;
-      E.zl[s].on = true; E.zl[s].d = z; E.zl[s].mp = mp;
-      E.zl_skip[s - 1] = 1;
-      any = true;
-      slab_elems = std::max<int64_t>(slab_elems, (int64_t)S * z.U * ZM);
-      E.step_partials[s] = (z.U / 16) * S;        // one abs-sum partial per workgroup (of its slab piece)
-    }
-    if (any) {
-      for (int s = 3; s + 1 < P.n_steps; ++s) {   // links of the chain: the pair (s - 1, s) takes the result of the pair (s - 3, s - 2)
-        if (!E.zl[s].on || !E.zl[s - 2].on || P.steps[s - 1].lhs != P.steps[s - 2].out) continue;
-        if (E.zl[s - 2].d.U != ZM || E.zl[s - 2].mp != E.zl[s].mp || E.zl[s - 2].d.ldC != E.zl[s].d.ldE) continue;
-        E.zl[s].from_prev = true;
-        E.zl[s].buf = E.zl[s - 2].buf ^ 1;
-        E.zl[s - 2].feeds_next = true;
-      }
-      E.part_slots = 0;
-      for (int s = 0; s < P.n_steps; ++s) { E.step_off[s] = E.part_slots; E.part_slots += E.step_partials[s]; }
-      for (int i = 0; i < 2; ++i) HIPCHECK_X(hipMalloc((void**)&E.d_zl_slab[i], (size_t)replicas * slab_elems * 4));
-    } else {
-      E.zl.clear(); E.zl_skip.clear();
-    }
-  }
-  // complex x complex step pairs (k_cmfma_f32): only on request (CTN_CPLX=1) while kCplxDefault is off
-  if (!P.chain && P.dtype == CTN_F32 && (E.sw.cplx == 1 || (kCplxDefault && E.sw.cplx != 0))) {
-    E.cplx.assign(P.n_steps, CplxDesc());
-    E.cplx_skip.assign(P.n_steps, 0);
-    std::vector<int32_t> tabs;
-    bool any = false;
-    for (int s = 1; s < P.n_steps; ++s) {
-      if ((!E.zip.empty() && (E.zip[s].on || E.zip_skip[s])) || (!E.zl.empty() && (E.zl[s].on || E.zl_skip[s])))
-        continue;      // (a zipper pair is two GEMM steps: its members never have an S step behind them)
-      CplxDesc cd;
-      if (!cplx_match(P, s, &cd, &tabs)) continue;
-      const int64_t tiles = (int64_t)((cd.Mx + CX_TX - 1) / CX_TX) * ((cd.Ny + CX_TY - 1) / CX_TY);
-      E.cplx[s] = cd;
-      E.cplx_skip[cd.sp] = 1;
-      any = true;
-      // one abs-sum partial per workgroup of the fused launch (beyond the slots: collapsed to one); the skipped S step
-      // keeps its (never written, zero) slots: its rescale reads 0.0
-      E.step_partials[s] = tiles > kMaxPartials ? 1 : (int)tiles;
-      scratch_need = std::max<int64_t>(scratch_need, tiles);
-    }
-    if (any) {
-      E.part_slots = 0;
-      for (int s = 0; s < P.n_steps; ++s) { E.step_off[s] = E.part_slots; E.part_slots += E.step_partials[s]; }
-      HIPCHECK_X(hipMalloc((void**)&E.d_cplx_tabs, tabs.size() * 4));
-      HIPCHECK_X(hipMemcpy(E.d_cplx_tabs, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
-    } else {
-      E.cplx.clear(); E.cplx_skip.clear();
-    }
-  }
-  // full dots against a transposed tensor
-  if (!P.chain && E.sw.dot_tr) {
-    E.dot_tr.assign(P.n_steps, Exec::DotTr());
-    bool any = false;
-    for (int s = 0; s < P.n_steps; ++s) any = dot_tr_match(P, P.steps[s], &E.dot_tr[s]) || any;
-    if (!any) E.dot_tr.clear();
-  }
-  // steps with a resident left operand (k_mfma_f32_ares)
-  if (!P.chain && E.sw.ares != 0 && P.dtype == CTN_F32) {
-    E.ares_ntw.assign(P.n_steps, 0);
-    bool any = false;
-    for (int s = 0; s < P.n_steps; ++s) { E.ares_ntw[s] = ares_match(P, s, replicas, E.n_cu, E.sw);
-      if (E.ares_ntw[s] && ares_avec(P, s)) E.ares_ntw[s] |= 1 << 16;
-      any = any || E.ares_ntw[s];
-    }
-    if (!any) E.ares_ntw.clear();
-  }
-  // a sweep: at least half a chip of row blocks, or CTN_SWEEP=1
-  if (!P.chain && E.sw.sweep != 0 && P.stabilize) {
-    Exec::SweepDesc sd;
-    // (bonds up to 128: the per-site launches are a few microseconds of latency each whatever the batch - always)
-    if (sweep_match(P, &sd) && (int)sd.steps.size() <= kSweepMaxSites &&
-        (E.sw.sweep == 1 || (sd.steps.size() >= 4 && (sd.D <= 128 || (int64_t)sd.J * replicas * 2 >= E.n_cu)))) {
-      E.sweep = sd;
-      const int S = (int)sd.steps.size();
-      E.sweep_role.assign(P.n_steps, 0);
-      std::vector<int32_t> ids((size_t)S * 2), slots((size_t)S);
-      std::vector<int64_t> offs((size_t)S);
-      for (int i = 0; i < S; ++i) {
-        const int s = sd.steps[i];
-        E.sweep_role[s] = i + 1 == S ? 2 : 1;
-        ids[2 * i] = P.steps[s].rhs; ids[2 * i + 1] = P.steps[s].lhs2;
-        offs[i] = E.step_off[s]; slots[i] = E.step_partials[s];
-      }
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_ids, ids.size() * 4));
-      HIPCHECK_X(hipMemcpy(E.d_sweep_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_off, offs.size() * 8));
-      HIPCHECK_X(hipMemcpy(E.d_sweep_off, offs.data(), offs.size() * 8, hipMemcpyHostToDevice));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_slots, slots.size() * 4));
-      HIPCHECK_X(hipMemcpy(E.d_sweep_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-      const size_t nrec = (size_t)replicas * S * sd.J;
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_a, nrec * 8));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_s, nrec * 4));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_z, (size_t)replicas * S * 8));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_la, nrec * 8));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_ls, nrec * 8));
-    } else if (P.dtype == CTN_F64 && E.sw.sweep64 != 0 && (E.sw.sweep == 1 || kSweepF64Default) && sweep64_match(P, &sd) &&
-               (int)sd.steps.size() <= 2 * kSweepMaxSites) {
-      // float64 (k_sweep_f64): the run's 2 S steps are all members - a GEMM and a streaming step per site
-      E.sweep = sd;
-      const int T = (int)sd.steps.size(), S = T / 2;
-      E.sweep_role.assign(P.n_steps, 0);
-      std::vector<int32_t> slots((size_t)T);
-      std::vector<int64_t> offs((size_t)T);
-      for (int i = 0; i < T; ++i) {
-        const int s = sd.steps[i];
-        E.sweep_role[s] = i + 1 == T ? 2 : 1;
-        offs[i] = E.step_off[s]; slots[i] = E.step_partials[s];
-      }
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_ids, sd.ids.size() * 4));
-      HIPCHECK_X(hipMemcpy(E.d_sweep_ids, sd.ids.data(), sd.ids.size() * 4, hipMemcpyHostToDevice));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_off, offs.size() * 8));
-      HIPCHECK_X(hipMemcpy(E.d_sweep_off, offs.data(), offs.size() * 8, hipMemcpyHostToDevice));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_slots, slots.size() * 4));
-      HIPCHECK_X(hipMemcpy(E.d_sweep_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
-      const size_t nrec = (size_t)replicas * S * sd.J;
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_a, 2 * nrec * 8));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_e, nrec * 4));
-      HIPCHECK_X(hipMalloc((void**)&E.d_sweep_z, (size_t)replicas * T * 8));
-    }
-  }
-  // leaf groups: runs of consecutive plain streaming steps on network inputs, same kernel variant (see Exec::LeafGroup)
-  if (!P.chain && E.sw.group) {
-    E.groups.assign(P.n_steps, Exec::LeafGroup());
-    auto leaf = [&](int s, int* vw, int* u) {
-      const Step& st = P.steps[s];
-      if (st.kernel != CTN_KERNEL_ELEMENT || st.kvec || st.collapse || s + 1 >= P.n_steps || st.rhs < 0 ||
-          st.lhs >= P.n_inputs || st.rhs >= P.n_inputs || st.lhs2 >= 0 || stream_splits(st, replicas, E.n_cu) ||
-          (!E.cplx_skip.empty() && E.cplx_skip[s]))      // (the S step of a complex pair is never launched)
-        return false;
-      int64_t nq;
-      *vw = st.vecw;
-      stream_variant(st, replicas, *vw, u, &nq);
-      return true;
-    };
-    int total = 0;
-    for (int s = 0; s < P.n_steps;) {
-      int vw, u;
-      if (!leaf(s, &vw, &u)) { ++s; continue; }
-      int e = s + 1, blocks = P.steps[s].blocks, vw2, u2;
-      while (e < P.n_steps && e - s < 1024 && leaf(e, &vw2, &u2) && vw2 == vw && u2 == u) { blocks = std::max(blocks, P.steps[e].blocks); ++e; }
-      if (e - s >= 2) {
-        Exec::LeafGroup& G = E.groups[s];
-        G.len = e - s; G.vw = vw; G.u = u; G.blocks = blocks; G.off = total;
-        total += G.len;
-      }
-      s = e;
-    }
-    if (total) {
-      HIPCHECK_X(hipHostMalloc((void**)&E.h_group_args, sizeof(StepArgs) * (size_t)total, hipHostMallocDefault));
-      HIPCHECK_X(hipMalloc((void**)&E.d_group_args, sizeof(StepArgs) * (size_t)total));
-    } else {
-      E.groups.clear();
-    }
-  }
-  HIPCHECK_X(hipMalloc((void**)&E.d_scratch, (size_t)replicas * scratch_need * 8));
-  HIPCHECK_X(hipMalloc((void**)&E.d_partials, (size_t)E.part_slots * replicas * 8));
-  HIPCHECK_X(hipMemset(E.d_partials, 0, (size_t)E.part_slots * replicas * 8));
-  {
-    std::vector<int32_t> slots(E.step_partials.begin(), E.step_partials.end());
-    HIPCHECK_X(hipMalloc((void**)&E.d_stepOff, P.n_steps * 8));
-    HIPCHECK_X(hipMalloc((void**)&E.d_stepSlots, P.n_steps * 4));
-    HIPCHECK_X(hipMemcpy(E.d_stepOff, E.step_off.data(), P.n_steps * 8, hipMemcpyHostToDevice));
-    HIPCHECK_X(hipMemcpy(E.d_stepSlots, slots.data(), P.n_steps * 4, hipMemcpyHostToDevice));
-  }
+  HIPCHECK_X(dev_alloc(&E.d_slab, F.slab_elems * P.elem_size()));
+  HIPCHECK_X(dev_alloc(&E.d_slab2, F.fold_elems * P.elem_size()));
+  for (int i = 0; i < 2; ++i) HIPCHECK_X(dev_alloc(&E.d_zl_slab[i], (size_t)F.zl_slab_elems * 4));
+  HIPCHECK_X(dev_upload(&E.d_cplx_tabs, F.cplx_tabs));
+  HIPCHECK_X(dev_upload(&E.d_sweep_ids, F.sweep_ids));
+  HIPCHECK_X(dev_upload(&E.d_sweep_off, F.sweep_offs));
+  HIPCHECK_X(dev_upload(&E.d_sweep_slots, F.sweep_slots));
+  HIPCHECK_X(dev_alloc(&E.d_sweep_a, F.sweep_a * 8));
+  HIPCHECK_X(dev_alloc(&E.d_sweep_s, F.sweep_s * 4));
+  HIPCHECK_X(dev_alloc(&E.d_sweep_e, F.sweep_e * 4));
+  HIPCHECK_X(dev_alloc(&E.d_sweep_z, F.sweep_z * 8));
+  HIPCHECK_X(dev_alloc(&E.d_sweep_la, F.sweep_l * 8));
+  HIPCHECK_X(dev_alloc(&E.d_sweep_ls, F.sweep_l * 8));
+  if (F.group_args) HIPCHECK_X(hipHostMalloc((void**)&E.h_group_args, sizeof(StepArgs) * (size_t)F.group_args, hipHostMallocDefault));
+  HIPCHECK_X(dev_alloc(&E.d_group_args, sizeof(StepArgs) * (size_t)F.group_args));
+  HIPCHECK_X(hipMalloc((void**)&E.d_scratch, (size_t)replicas * F.scratch_need * 8));
+  HIPCHECK_X(hipMalloc((void**)&E.d_partials, (size_t)F.part_slots * replicas * 8));
+  HIPCHECK_X(hipMemset(E.d_partials, 0, (size_t)F.part_slots * replicas * 8));
+  HIPCHECK_X(dev_upload(&E.d_stepOff, F.step_off));
+  HIPCHECK_X(dev_upload(&E.d_stepSlots, F.step_partials));
   HIPCHECK_X(hipMalloc((void**)&E.d_log, (size_t)replicas * 8));
   HIPCHECK_X(hipMalloc((void**)&E.d_resc, (size_t)replicas * P.n_steps * 8));
   HIPCHECK_X(hipMalloc((void**)&E.d_logs, (size_t)replicas * P.n_steps * 8));
@@ -1991,13 +1335,11 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   std::vector<int32_t> sp(P.n_steps);
   std::vector<double> sn(P.n_steps);
   for (int s = 0; s < P.n_steps; ++s) {
-    sp[s] = P.steps[s].kernel == CTN_KERNEL_FUSED ? 0 : E.step_partials[s];   // no partials: rescale reported as 0.0
+    sp[s] = P.steps[s].kernel == CTN_KERNEL_FUSED ? 0 : F.step_partials[s];   // no partials: rescale reported as 0.0
     sn[s] = (double)P.tensors[P.steps[s].out].numel;
   }
-  HIPCHECK_X(hipMalloc((void**)&E.d_stepP, P.n_steps * 4));
-  HIPCHECK_X(hipMalloc((void**)&E.d_stepNumel, P.n_steps * 8));
-  HIPCHECK_X(hipMemcpy(E.d_stepP, sp.data(), P.n_steps * 4, hipMemcpyHostToDevice));
-  HIPCHECK_X(hipMemcpy(E.d_stepNumel, sn.data(), P.n_steps * 8, hipMemcpyHostToDevice));
+  HIPCHECK_X(dev_upload(&E.d_stepP, sp));
+  HIPCHECK_X(dev_upload(&E.d_stepNumel, sn));
   if (P.chain) {
     std::vector<ChainStep> cs(P.n_steps);
     for (int s = 0; s < P.n_steps; ++s) {
@@ -2014,54 +1356,25 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
       c.prodA = st.lhs >= P.n_inputs ? P.tensors[st.lhs].producer : -1;
       c.prodB = st.rhs >= P.n_inputs ? P.tensors[st.rhs].producer : -1;
     }
-    HIPCHECK_X(hipMalloc((void**)&E.d_chain, cs.size() * sizeof(ChainStep)));
-    HIPCHECK_X(hipMemcpy(E.d_chain, cs.data(), cs.size() * sizeof(ChainStep), hipMemcpyHostToDevice));
+    HIPCHECK_X(dev_upload(&E.d_chain, cs));
     // the on-chip walker, where asked for and where the packer takes the plan (a refusal keeps k_chain)
     if (E.sw.chain == 2 || (kChainLdsDefault && E.sw.chain != 1)) {
       ChainProgram cp;
       std::string why;
       if (chain_pack(P, &cp, &why)) {
-        HIPCHECK_X(hipMalloc((void**)&E.d_chain_prog, cp.words.size() * 4));
-        HIPCHECK_X(hipMemcpy(E.d_chain_prog, cp.words.data(), cp.words.size() * 4, hipMemcpyHostToDevice));
+        HIPCHECK_X(dev_upload(&E.d_chain_prog, cp.words));
         E.chain_len0 = cp.steps[0].len;
       }
     }
   }
-  // k_zipqp_f32: a result that would overwrite the pair's E moves to a side buffer.  A buffer is free again once the
-  // step that consumes its tensor has been launched (every intermediate is consumed exactly once): a chain needs two.
-  if (!E.zip.empty()) {
-    const int64_t es = P.elem_size();
-    std::vector<int> busy_until;                        // per side buffer: the step that reads what it holds
-    for (int s = 1; s + 1 < P.n_steps; ++s) {
-      if (!E.zip[s].on || !E.zip[s].zqp) continue;
-      const int idE = P.steps[s - 1].lhs, idC = P.steps[s].out;
-      if (idE < P.n_inputs) continue;
-      const int64_t e0 = P.tensors[idE].ws_offset, e1 = e0 + P.tensors[idE].numel * es;
-      const int64_t c0 = P.tensors[idC].ws_offset, c1 = c0 + P.tensors[idC].numel * es;
-      const bool e_in_ws = E.zqp_side.empty() || E.zqp_side[idE] < 0;       // (an E that moved itself is out of the way)
-      if (!e_in_ws || c0 >= e1 || e0 >= c1) continue;
-      if (E.zqp_side.empty()) E.zqp_side.assign((size_t)E.n_tensors, -1);
-      int consumer = P.n_steps;
-      for (int c = s + 1; c < P.n_steps; ++c)
-        if (P.steps[c].lhs == idC || P.steps[c].rhs == idC || P.steps[c].lhs2 == idC) { consumer = c; break; }
-      int k = 0;
-      while (k < (int)busy_until.size() && busy_until[k] >= s - 1) ++k;      // (E's own buffer is read by step s - 1)
-      if (k == (int)busy_until.size()) busy_until.push_back(0);
-      busy_until[k] = consumer;
-      E.zqp_side[idC] = k;
-      E.zqp_side_bytes = std::max<int64_t>(E.zqp_side_bytes, (c1 - c0 + 255) / 256 * 256);
-    }
-    if (!busy_until.empty())
-      HIPCHECK_X(hipMalloc((void**)&E.d_zqp_side, (size_t)E.zqp_side_bytes * busy_until.size() * replicas));
-  }
+  HIPCHECK_X(dev_alloc(&E.d_zqp_side, (size_t)F.zqp_side_bytes * F.zqp_side_bufs * replicas));
   // pointer table: intermediates and the ones-scalar are fixed for the executor's lifetime
   E.h_ptrs.assign((size_t)replicas * E.n_tensors, nullptr);
   for (int r = 0; r < replicas; ++r) {
     void** row = E.h_ptrs.data() + (size_t)r * E.n_tensors;
     for (int id = P.n_inputs; id < P.n_inputs + P.n_steps - 1; ++id)
-      row[id] = E.zqp_side.empty() || E.zqp_side[id] < 0
-                    ? E.d_ws + (size_t)r * P.ws_bytes_per_replica + P.tensors[id].ws_offset
-                    : E.d_zqp_side + ((size_t)E.zqp_side[id] * replicas + r) * E.zqp_side_bytes;
+      row[id] = F.zqp_side[id] < 0 ? E.d_ws + (size_t)r * P.ws_bytes_per_replica + P.tensors[id].ws_offset
+                                   : E.d_zqp_side + ((size_t)F.zqp_side[id] * replicas + r) * F.zqp_side_bytes;
     row[E.n_tensors - 1] = E.d_ones;
   }
 #undef HIPCHECK_X
@@ -2121,18 +1434,17 @@ static bool exec_scales_suspect(const Exec* E, const double* resc = nullptr, int
         return v == 0.0 ? 1.0 : v;
       };
       if (st.kernel == CTN_KERNEL_FUSED) continue;
-      if (!E->zip_skip.empty() && E->zip_skip[s]) continue;          // runs inside the next step's launch
-      if (!E->zl_skip.empty() && E->zl_skip[s]) continue;
-      if (!E->cplx_skip.empty() && E->cplx_skip[s]) continue;
-      if (!E->sweep_role.empty() && E->sweep_role[s] && !E->eager_rescale) {   // a sweep keeps its products in range by itself
+      const Role role = E->forms.role[s];
+      if (role == Role::Absorbed) continue;                          // runs inside a later step's launch
+      if (E->forms.sweep_role[s] && !E->eager_rescale) {             // a sweep keeps its products in range by itself
         if (!std::isfinite(rs[s])) return true;
         continue;
       }
       double sab = scale_of(st.lhs) * (st.rhs >= 0 ? scale_of(st.rhs) : 1.0) * (st.lhs2 >= 0 ? scale_of(st.lhs2) : 1.0);
-      if ((!E->zip.empty() && E->zip[s].on) || (!E->zl.empty() && E->zl[s].on))   // the fused pair accumulates on E, X and Y as stored
+      if (role == Role::Zip || role == Role::ZipLat)                 // the fused pair accumulates on E, X and Y as stored
         sab = scale_of(P.steps[s - 1].lhs) * scale_of(P.steps[s - 1].rhs) * scale_of(st.rhs);
-      if (!E->cplx.empty() && E->cplx[s].on)                         // the complex pair accumulates on `small` and `big` as stored
-        sab = scale_of(E->cplx[s].small) * scale_of(E->cplx[s].big);
+      if (role == Role::Cplx)                                        // the complex pair accumulates on `small` and `big` as stored
+        sab = scale_of(E->forms.cplx[s].small) * scale_of(E->forms.cplx[s].big);
       const double so = rs[s];
       if (!std::isfinite(so) || !std::isfinite(sab)) return true;
       if (so == 0.0) { if (sab > zhi || sab < zlo) return true; continue; }

@@ -33,10 +33,10 @@ EXACT_ZIPQ = [((32, 128, 2), 3), ((48, 128, 4), 9), ((144, 384, 2), 3), ((256, 2
 
 def zipq_default():
     """`kZipQDefault` as the engine's source states it: is k_zipq_f32 taken without CTN_ZIPQ=1?"""
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "contractn_amd", "csrc", "engine.hip")
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "contractn_amd", "csrc", "fused_forms.h")
     with open(src) as fh:
         m = re.search(r"static constexpr bool kZipQDefault = (true|false);", fh.read())
-    assert m, "kZipQDefault not found in engine.hip"
+    assert m, "kZipQDefault not found in fused_forms.h"
     return m.group(1) == "true"
 
 
