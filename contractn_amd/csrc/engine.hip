@@ -51,6 +51,7 @@
 #include "kernels_zipm64.h"
 #include "kernels_zip_f64.h"
 #include "kernels_zipl.h"
+#include "kernels_zipl_f64.h"
 #include "kernels_sweep.h"
 #include "kernels_sweep_f64.h"
 #include "kernels_mfma_lat.h"
@@ -69,7 +70,7 @@ thread_local std::string g_err;
 
 static_assert(kFormGM == GM && kFormGK == GK && kFormDN == DN && kFormLatMaxK == kLatMaxK,
               "launch_form.h selects kernels by these values of theirs");
-static_assert(kFormZM == ZM && kFormZU == ZU && kFormZK == ZK && kFormZDU == ZDU && kFormZDK == ZDK && kFormZ6U == Z6U && kFormZ6K == Z6K &&
+static_assert(kFormZM == ZM && kFormZU == ZU && kFormZK == ZK && kFormZDU == ZDU && kFormZDK == ZDK && kFormZLD_MP == ZLD_MP && kFormZ6U == Z6U && kFormZ6K == Z6K &&
                   kFormZ1M == Z1M && kFormZ1U == Z1U && kFormZ1K == Z1K && kFormZ4M == Z4M && kFormZ4U == Z4U && kFormZ4K == Z4K &&
                   kFormSWR == SWR && kFormSweepMaxSites == kSweepMaxSites && kFormArM == AR_M && kFormArK == AR_K && kFormArTN == AR_TN,
               "fused_forms.h matches plans against these values of theirs");
@@ -115,7 +116,7 @@ struct Exec {
   // the buffers below: decided by fused_forms() (fused_forms.h) when the executor is created, read ever after.
   FusedForms forms;
   char* d_zqp_side = nullptr;          // k_zipqp_f32: [forms.zqp_side_bufs][R] side buffers of forms.zqp_side_bytes
-  float* d_zl_slab[2] = {nullptr, nullptr};   // latency pairs: [R][S][U][ZM] each, ping-pong along the chain
+  void* d_zl_slab[2] = {nullptr, nullptr};    // latency pairs: [R][S][U][ZM] each in the plan's dtype, ping-pong along the chain
   int32_t* d_cplx_tabs = nullptr;      // complex pairs: forms.cplx_tabs
   // the sweep's tables and records
   int32_t* d_sweep_ids = nullptr;      // [S][2] tensor ids (W_s, x_s)
@@ -564,9 +565,49 @@ static int launch_sweep_member(Exec* E, int s) {
   return rc != CTN_OK ? rc : t.end();
 }
 
+// a float64 zipper pair in its latency form (k_zip_lat_f64, CTN_ZIPL64=1): the same launch on the same descriptors
+static int launch_zip_lat_f64(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const ZipLat& L = E->forms.zl[s];
+  const ZipDesc& zd = L.d;
+  const Step& s1 = P.steps[s - 1];
+  const int S = ZLD_S, nub = zd.U / 16;
+  const bool eager = E->eager_rescale;
+  ZipLat64Args z{};
+  z.ptrs = E->d_ptrs; z.n_tensors = E->n_tensors;
+  z.idE = s1.lhs; z.idX = s1.rhs; z.idY = st.rhs;
+  z.slabs_in = (L.from_prev && !eager) ? (const double*)E->d_zl_slab[L.buf ^ 1] : nullptr;
+  z.slabs_out = (double*)E->d_zl_slab[L.buf];
+  z.ldE = zd.ldE; z.ldXq = zd.ldXq; z.ldXk = zd.ldXk; z.ldYq = zd.ldYq; z.ldYm = zd.ldYm;
+  z.U = zd.U; z.R = R;
+  producer_partials(E, s1.lhs, &z.partE, &z.PE, &z.strideE, &z.numelE);
+  z.min_norm = P.min_norm;
+  z.partC = part_region(E, s);
+  z.partC_stride = E->forms.step_partials[s];
+  const StepTimer t(E, s);
+  if (t.rc != CTN_OK) return t.rc;
+  E->launched_form[s] = CTN_FORM_ZIPL_F64;
+  report_tile(E, s, L.mp, ZM);      // (m1 part, all n2) per workgroup, 16 values of u: no plain fp64 form reports it
+  const dim3 gz((unsigned)((int64_t)R * nub * S));
+  if (zd.Q == 4 && z.slabs_in) hipLaunchKernelGGL((k_zip_lat_f64<4, true>), gz, dim3(512), 0, E->stream, z);
+  else if (zd.Q == 4) hipLaunchKernelGGL((k_zip_lat_f64<4, false>), gz, dim3(512), 0, E->stream, z);
+  else if (z.slabs_in) hipLaunchKernelGGL((k_zip_lat_f64<2, true>), gz, dim3(512), 0, E->stream, z);
+  else hipLaunchKernelGGL((k_zip_lat_f64<2, false>), gz, dim3(512), 0, E->stream, z);
+  if (!L.feeds_next || eager) {                 // nobody adds these slabs up while loading them: do it here
+    hipLaunchKernelGGL(k_zip_slab_sum_f64, dim3((unsigned)E->forms.step_partials[s], (unsigned)R), dim3(256), 0, E->stream,
+                       (const double*)z.slabs_out, S, zd.U, (void* const*)E->d_ptrs, E->n_tensors, st.out, zd.ldC, z.partC,
+                       z.partC_stride);
+    launch_renorm(E, s);
+  }
+  return t.end();
+}
+
 // a zipper pair in its latency form (k_zip_lat): steps (s - 1, s) as one launch, the result leaving as slabs
 static int launch_zip_lat(Exec* E, int s) {
   const Plan& P = *E->plan;
+  if (P.dtype == CTN_F64) return launch_zip_lat_f64(E, s);
   const Step& st = P.steps[s];
   const int R = E->R;
   const ZipLat& L = E->forms.zl[s];
@@ -577,8 +618,8 @@ static int launch_zip_lat(Exec* E, int s) {
   ZipLatArgs z{};
   z.ptrs = E->d_ptrs; z.n_tensors = E->n_tensors;
   z.idE = s1.lhs; z.idX = s1.rhs; z.idY = st.rhs;
-  z.slabs_in = (L.from_prev && !eager) ? E->d_zl_slab[L.buf ^ 1] : nullptr;
-  z.slabs_out = E->d_zl_slab[L.buf];
+  z.slabs_in = (L.from_prev && !eager) ? (const float*)E->d_zl_slab[L.buf ^ 1] : nullptr;
+  z.slabs_out = (float*)E->d_zl_slab[L.buf];
   z.ldE = zd.ldE; z.ldXq = zd.ldXq; z.ldXk = zd.ldXk; z.ldYq = zd.ldYq; z.ldYm = zd.ldYm;
   z.U = zd.U; z.R = R;
   producer_partials(E, s1.lhs, &z.partE, &z.PE, &z.strideE, &z.numelE);
@@ -1305,7 +1346,7 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   HIPCHECK_X(hipMalloc((void**)&E.d_ptrs, (size_t)replicas * E.n_tensors * sizeof(void*)));
   HIPCHECK_X(dev_alloc(&E.d_slab, F.slab_elems * P.elem_size()));
   HIPCHECK_X(dev_alloc(&E.d_slab2, F.fold_elems * P.elem_size()));
-  for (int i = 0; i < 2; ++i) HIPCHECK_X(dev_alloc(&E.d_zl_slab[i], (size_t)F.zl_slab_elems * 4));
+  for (int i = 0; i < 2; ++i) HIPCHECK_X(dev_alloc(&E.d_zl_slab[i], (size_t)F.zl_slab_elems * P.elem_size()));
   HIPCHECK_X(dev_upload(&E.d_cplx_tabs, F.cplx_tabs));
   HIPCHECK_X(dev_upload(&E.d_sweep_ids, F.sweep_ids));
   HIPCHECK_X(dev_upload(&E.d_sweep_off, F.sweep_offs));

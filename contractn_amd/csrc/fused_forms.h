@@ -24,6 +24,7 @@ namespace ctn {
 // kernels_mfma_ares.h)
 constexpr int kFormZM = 256, kFormZU = 128, kFormZK = 16;
 constexpr int kFormZDU = 64, kFormZDK = 8;
+constexpr int kFormZLD_MP = 32;                 // the part of m1 a workgroup of k_zip_lat_f64 owns (ZLD_MP of kernels_zipl_f64.h)
 constexpr int kFormZ6U = 64, kFormZ6K = 32;
 constexpr int kFormZ1M = 128, kFormZ1U = 128, kFormZ1K = 16;
 constexpr int kFormZ4M = 64, kFormZ4U = 64, kFormZ4K = 16;
@@ -39,8 +40,8 @@ struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0,
                  int zm = 256;                        // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
                  bool zq = false, zqp = false;        // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even); zqp: as k_zipqp_f32
                  int form = CTN_FORM_NONE; };         // the kernel that runs the pair (ctn_step_form), set where it is chosen
-// The same pair in its latency form (kernels_zipl.h): the fused launch of steps (s2 - 1, s2), whose result leaves as
-// slabs; from_prev = its E is the slabs of the pair before, feeds_next = the next pair adds its slabs up (else
+// The same pair in its latency form (kernels_zipl.h; float64: kernels_zipl_f64.h, mp = 32 always): the fused launch of
+// steps (s2 - 1, s2), whose result leaves as slabs; from_prev = its E is the slabs of the pair before, feeds_next = the next pair adds its slabs up (else
 // k_zip_slab_sum does); buf: which of the two slab buffers it writes (ping-pong along the chain)
 struct ZipLat { bool on = false, from_prev = false, feeds_next = false; int buf = 0, mp = 32; ZipDesc d; };
 // A sweep (kernels_sweep.h): a run of epilogue-summed GEMM steps, each on the result of the one before, walked by ONE
@@ -536,9 +537,22 @@ inline bool zip_pair_form(const Plan& P, int s, int R, int n_cu, const DevSwitch
   return true;
 }
 
-// The latency form of the same pair (k_zip_lat), if it has one
-inline bool zip_lat_form(const Plan& P, int s, int R, int n_cu, const DevSwitches& sw, ZipLat* out) {
+// Is k_zip_lat_f64 taken without CTN_ZIPL64=1 on a float64 plan with a few networks in flight?  Decided by measurement
+// (DESIGN sections 10 and 11).
+static constexpr bool kZipLatF64Default = false;
+
+// The latency form of the same pair (k_zip_lat; `dtype` CTN_F64: k_zip_lat_f64), if it has one
+inline bool zip_lat_form(const Plan& P, int s, int R, int n_cu, const DevSwitches& sw, ZipLat* out, int dtype = CTN_F32) {
   ZipDesc z;
+  if (dtype == CTN_F64) {
+    // fp64: a workgroup owns 32 of m1, always (64 does not fit its LDS; CTN_ZIPL_MP has no fp64 meaning); every leading
+    // dimension even: zip_match's own fp64 condition
+    if (!zip_match(P, s, &z, CTN_F64, 16)) return false;
+    if (z.K1 != kFormZM || (z.Q != 4 && z.Q != 2)) return false;
+    if ((z.U / 16) * (kFormZM / kFormZLD_MP) > kMaxPartials) return false;
+    out->on = true; out->d = z; out->mp = kFormZLD_MP;
+    return true;
+  }
   if (!zip_match(P, s, &z, CTN_F32, 16)) return false;
   if (z.K1 != kFormZM || (z.Q != 4 && z.Q != 2) || z.ldC % 4 || z.ldE % 4 || z.ldXk % 4 || z.ldXq % 4 || z.ldYm % 4 || z.ldYq % 4) return false;
   // the part of m1 a workgroup owns: 32 (8 slabs, 128 workgroups per network at |u| = 256) while that still fits ONE
@@ -592,12 +606,15 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.step_partials[s] = z.U / z.zu;
       any_zip = true;
     }
-  // the same pairs in their latency form: a few networks in flight (or CTN_ZIPL=1), and no throughput-form pair taken
-  if (P.dtype == CTN_F32 && !any_zip && sw.zipl != 0 && (sw.zipl == 1 || R <= sw.zipl_max_r)) {
+  // the same pairs in their latency form: a few networks in flight (or CTN_ZIPL=1), and no throughput-form pair taken;
+  // float64 (k_zip_lat_f64): only on request (CTN_ZIPL64=1) while kZipLatF64Default is off
+  const bool lat32 = P.dtype == CTN_F32 && sw.zipl != 0 && (sw.zipl == 1 || R <= sw.zipl_max_r);
+  const bool lat64 = P.dtype == CTN_F64 && (sw.zipl64 == 1 || (kZipLatF64Default && sw.zipl64 != 0 && R <= sw.zipl_max_r));
+  if (!any_zip && (lat32 || lat64)) {
     int64_t slab_elems = 0;
     for (int s = 1; s + 1 < n; ++s) {
       ZipLat L;
-      if (F.role[s - 1] != Role::Plain || !zip_lat_form(P, s, R, n_cu, sw, &L)) continue;
+      if (F.role[s - 1] != Role::Plain || !zip_lat_form(P, s, R, n_cu, sw, &L, P.dtype)) continue;
       if (F.zl.empty()) F.zl.assign(n, ZipLat());
       F.zl[s] = L;
       F.role[s] = Role::ZipLat; F.role[s - 1] = Role::Absorbed;

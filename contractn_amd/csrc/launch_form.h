@@ -60,6 +60,8 @@ struct DevSwitches {
   int g_big = 1;         // CTN_G_BIG=0: never the 256 x 256 tiles (experiments)
   int g_splitk = 1;      // CTN_G_SPLITK=0: no K split over workgroups on the large-tile kernel
   int zipl_mp = 0;       // CTN_ZIPL_MP=32|64: force the part of m1 a k_zip_lat workgroup owns (tests)
+  int zipl64 = -1;       // CTN_ZIPL64: 1 a float64 zipper pair runs as one latency-form launch (k_zip_lat_f64) wherever the pair
+                         // matches and no throughput form (CTN_ZIP=1) took it; 0 or unset: never (kZipLatF64Default)
   bool g_no_asm = false; // CTN_G_NO_ASM: C++ inner loop instead of the hand-scheduled blocks
   const char* stamps = nullptr;  // CTN_DEBUG_STAMPS=<file> (make STAMPS=1 builds): dump in-kernel cycle stamps
   int stamp_step = -1;   // CTN_DEBUG_STAMP_STEP=<s>: stamp only this step
@@ -85,6 +87,7 @@ inline DevSwitches read_dev_switches() {
   d.chain = num("CTN_CHAIN", -1);
   d.zipl_max_r = num("CTN_ZIPL_MAX_R", 8);
   d.zipl_mp = num("CTN_ZIPL_MP", 0);
+  d.zipl64 = num("CTN_ZIPL64", -1);
   d.g_splitk = num("CTN_G_SPLITK", 1);
   d.g_big = num("CTN_G_BIG", 1);
   d.ares = num("CTN_ARES", -1);

@@ -178,7 +178,8 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                      reports sum over slabs of sum |slab| / numel >= sum |E'| / numel (the true mean within the
  *                      number of slabs, 4 or 8) unless k_zip_slab_sum runs behind it; the step that consumes the
  *                      slabs divides by the same number, so the product of all factors is still the reference's
- *                      (the log register to rounding, 1e-4 in the tests), the individual factors are not;
+ *                      (the log register to rounding, 1e-4 in the tests), the individual factors are not.  The fp64
+ *                      latency form (k_zip_lat_f64, CTN_ZIPL64=1; 8 slabs) reports bounds exactly as k_zip_lat does;
  *                    - the S step of a complex x complex step run as one launch (k_cmfma_f32, CTN_CPLX=1: the
  *                      streaming step that contracts the 2 x 2 x 2 structure tensor into the smaller operand, and the
  *                      GEMM that is the only consumer of its result): the widened operand never exists, the S step
@@ -283,6 +284,7 @@ int ctn_exec_merge_scales(ctn_exec* exec, int t_dtype, void* buf, int64_t stride
  * A step that runs inside the launch of a later one (see step_rescales above) reports (1, 1); the fused forms report
  * tiles no plain form has: the zipper pairs (512, 256), (512, 128), (512, 64), (256, 32), (32, 256), (64, 256 with
  * (1, 1) before it); a sweep (16, D P); the complex pair k_cmfma_f32 (64, 256) behind the (1, 1) of its S step.
+ * The fp64 latency form k_zip_lat_f64 reports (32, 256) behind the (1, 1) of its absorbed step, exactly as k_zip_lat does.
  */
 int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t* tile_n);
 
@@ -301,7 +303,8 @@ typedef enum {
   CTN_FORM_ZIP128 = 4,  /* k_zip128_f32 */
   CTN_FORM_ZIPM64 = 5,  /* k_zipm64_f32 */
   CTN_FORM_ZIP_F64 = 6, /* k_zip_f64 */
-  CTN_FORM_ZIPQP = 7    /* k_zipqp_f32: k_zipq_f32 with a workgroup that walks several work items of the launch */
+  CTN_FORM_ZIPQP = 7,   /* k_zipqp_f32: k_zipq_f32 with a workgroup that walks several work items of the launch */
+  CTN_FORM_ZIPL_F64 = 8 /* k_zip_lat_f64: the float64 latency form, tile (32, 256) (the fp32 latency form k_zip_lat reports NONE) */
 } ctn_step_form;
 int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form);
 
