@@ -49,6 +49,7 @@
 #include "kernels_zip64.h"
 #include "kernels_zip128.h"
 #include "kernels_zipm64.h"
+#include "kernels_zip512.h"
 #include "kernels_zip_f64.h"
 #include "kernels_zipl.h"
 #include "kernels_zipl_f64.h"
@@ -71,7 +72,7 @@ thread_local std::string g_err;
 static_assert(kFormGM == GM && kFormGK == GK && kFormDN == DN && kFormLatMaxK == kLatMaxK,
               "launch_form.h selects kernels by these values of theirs");
 static_assert(kFormZM == ZM && kFormZU == ZU && kFormZK == ZK && kFormZDU == ZDU && kFormZDK == ZDK && kFormZLD_MP == ZLD_MP && kFormZ6U == Z6U && kFormZ6K == Z6K &&
-                  kFormZ1M == Z1M && kFormZ1U == Z1U && kFormZ1K == Z1K && kFormZ4M == Z4M && kFormZ4U == Z4U && kFormZ4K == Z4K &&
+                  kFormZ1M == Z1M && kFormZ1U == Z1U && kFormZ1K == Z1K && kFormZ4M == Z4M && kFormZ4U == Z4U && kFormZ4K == Z4K && kFormZ5M == Z5M && kFormZ5U == Z5U && kFormZ5K == Z5K &&
                   kFormSWR == SWR && kFormSweepMaxSites == kSweepMaxSites && kFormArM == AR_M && kFormArK == AR_K && kFormArTN == AR_TN,
               "fused_forms.h matches plans against these values of theirs");
 
@@ -666,7 +667,9 @@ static void launch_renorm(Exec* E, int s) {
 // The tile is 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256): an fp64
 // step with 128 tile columns reads as k_mfma_f64_g.  k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a
 // wave sums; k_zipm64_f32 (bond 64) likewise (256, 32): its 256 threads, 32 values of m1 per wave - a tile no plain
-// form reports (theirs are 16 x 16 or have 64 columns at least)
+// form reports (theirs are 16 x 16 or have 64 columns at least).  k_zip512_f32 (bond 512) reports (512, 512): its 512
+// threads and all 512 n2 - plain tiles have at most 256 rows, and no other pair kernel has 512 columns.  (Index 8,
+// CTN_FORM_ZIPL_F64, is the float64 latency form: it has a launcher of its own and no row here.)
 struct ZipKernel { void (*kernel)(ZipArgs); int threads, tm, tn; bool walks; };
 static const ZipKernel kZipKernels[] = {
     {nullptr, 0, 0, 0, false},                // CTN_FORM_NONE
@@ -677,9 +680,13 @@ static const ZipKernel kZipKernels[] = {
     {k_zipm64_f32, 256, 256, 32, false},      // CTN_FORM_ZIPM64
     {k_zip_f64, 512, 512, 256, false},        // CTN_FORM_ZIP_F64
     {k_zipqp_f32, 256, 512, 256, true},       // CTN_FORM_ZIPQP
+    {nullptr, 0, 0, 0, false},                // CTN_FORM_ZIPL_F64: launch_zip_lat's
+    {k_zip512_f32, 512, 512, 512, false},     // CTN_FORM_ZIP512
 };
 static_assert(CTN_FORM_ZIP == 1 && CTN_FORM_ZIPQ == 2 && CTN_FORM_ZIP64 == 3 && CTN_FORM_ZIP128 == 4 && CTN_FORM_ZIPM64 == 5 &&
-              CTN_FORM_ZIP_F64 == 6 && CTN_FORM_ZIPQP == 7, "kZipKernels is indexed by ctn_step_form");
+              CTN_FORM_ZIP_F64 == 6 && CTN_FORM_ZIPQP == 7 && CTN_FORM_ZIPL_F64 == 8 && CTN_FORM_ZIP512 == 9 &&
+                  sizeof(kZipKernels) / sizeof(kZipKernels[0]) == 10,
+              "kZipKernels is indexed by ctn_step_form");
 
 // a zipper pair: steps (s - 1, s) as one launch
 static int launch_zip(Exec* E, int s) {

@@ -5,7 +5,7 @@
 //
 // Every argument is one setting: the networks in flight (R, default 1), the chip's CUs (CU, default 256) and development
 // switches by the names of their environment variables without the CTN_ prefix (ZIP, ZIPQ, ZIPL, ZIPL_MP, ZIPL_MAX_R, ZIPL64,
-// ZIP128, ZIPM64, CPLX, SWEEP, SWEEP64, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
+// ZIP128, ZIPM64, ZIP512, CPLX, SWEEP, SWEEP64, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
 // environment is not read.  For every plan and every setting one line goes to stdout with everything an executor would
 // decide when it is created:
 //
@@ -52,6 +52,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     else if (key == "ZIPL64") d.zipl64 = v;
     else if (key == "ZIP128") d.zip128 = v;
     else if (key == "ZIPM64") d.zipm64 = v;
+    else if (key == "ZIP512") d.zip512 = v;
     else if (key == "CPLX") d.cplx = v;
     else if (key == "SWEEP") d.sweep = v;
     else if (key == "SWEEP64") d.sweep64 = v;

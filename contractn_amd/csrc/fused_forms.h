@@ -19,7 +19,7 @@ namespace ctn {
 
 // What the rules below know of the kernels (engine.hip asserts that these are the kernels' own values): the zipper-pair
 // kernels' |m1| = |n2|, values of u per workgroup and phase-1 tile depth (ZM, ZU, ZK of kernels_zip.h; ZD*: kernels_zip_f64.h,
-// Z6*: kernels_zip64.h, Z1*: kernels_zip128.h, Z4*: kernels_zipm64.h), the sweeps' inputs per workgroup and most sites
+// Z6*: kernels_zip64.h, Z1*: kernels_zip128.h, Z4*: kernels_zipm64.h, Z5*: kernels_zip512.h), the sweeps' inputs per workgroup and most sites
 // (SWR, kSweepMaxSites of kernels_sweep.h), and the resident-operand kernel's M, K and column tile (AR_M, AR_K, AR_TN of
 // kernels_mfma_ares.h)
 constexpr int kFormZM = 256, kFormZU = 128, kFormZK = 16;
@@ -28,16 +28,18 @@ constexpr int kFormZLD_MP = 32;                 // the part of m1 a workgroup of
 constexpr int kFormZ6U = 64, kFormZ6K = 32;
 constexpr int kFormZ1M = 128, kFormZ1U = 128, kFormZ1K = 16;
 constexpr int kFormZ4M = 64, kFormZ4U = 64, kFormZ4K = 16;
+constexpr int kFormZ5M = 512, kFormZ5U = 64, kFormZ5K = 8;
 constexpr int kFormSWR = 16, kFormSweepMaxSites = 1024;
 constexpr int kFormArM = 256, kFormArK = 256, kFormArTN = 128;
 static_assert(kFormZ1K == kFormZK, "zip_match checks K1 against ZK; k_zip128_f32's tile depth must be the same");
 static_assert(kFormZ4K == kFormZK, "zip_match checks K1 against ZK; k_zipm64_f32's tile depth must be the same");
+static_assert(kFormZK % kFormZ5K == 0, "zip_match checks K1 against ZK; k_zip512_f32's tile depth must divide it");
 
 // A zipper pair (kernels_zip.h): the fused launch of steps (s2 - 1, s2); the first step of such a pair is never launched
 // (its result only exists in the fused kernel's registers)
 struct ZipDesc { bool on = false; int64_t ldE = 0, ldXq = 0, ldXk = 0, ldYq = 0, ldYm = 0, ldC = 0; int Q = 0, U = 0, K1 = 0;
                  int zu = 128; bool f64 = false;      // zu: values of u per workgroup (128: k_zip_f32, 64: k_zip64_f32, k_zip_f64)
-                 int zm = 256;                        // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64)
+                 int zm = 256;                        // zm: |m1| = |n2| (256; 128: k_zip128_f32, zu = 128; 64: k_zipm64_f32, zu = 64; 512: k_zip512_f32, zu = 64)
                  bool zq = false, zqp = false;        // zq: k_zipq_f32 runs the pair (zu = 128, zm = 256, Q even); zqp: as k_zipqp_f32
                  int form = CTN_FORM_NONE; };         // the kernel that runs the pair (ctn_step_form), set where it is chosen
 // The same pair in its latency form (kernels_zipl.h; float64: kernels_zipl_f64.h, mp = 32 always): the fused launch of
@@ -71,8 +73,10 @@ static constexpr bool kZipF64Default = false;
 static constexpr bool kZip128Default = false;
 // Is k_zipm64_f32 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement.
 static constexpr bool kZipM64Default = false;
+// Is k_zip512_f32 taken without CTN_ZIP=1 when its launch fills the chip?  Decided by measurement (DESIGN sections 10 and 11).
+static constexpr bool kZip512Default = false;
 
-// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32; `zm` = 128: k_zip128_f32, 64: k_zipm64_f32) or k_zip_f64 (CTN_F64)
+// Do steps (s2 - 1, s2) form a zipper pair that k_zip_f32 (`dtype` CTN_F32; `zm` = 128: k_zip128_f32, 64: k_zipm64_f32, 512: k_zip512_f32) or k_zip_f64 (CTN_F64)
 // can run as one launch?
 // Checked on the plan's own offset tables (every operand dense along its innermost index with uniform strides), so
 // nothing about the network's labels is assumed: T = E . X with |m1| = zm rows from E, columns (q, u) from X;
@@ -531,6 +535,14 @@ inline bool zip_pair_form(const Plan& P, int s, int R, int n_cu, const DevSwitch
       z.K1 % kFormZ4K == 0 && z.K1 >= 2 * kFormZ4K && ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
       (sw.zip == 1 || (kZipM64Default && (int64_t)(z.U / kFormZ4U) * R >= n_cu && fill((int64_t)(z.U / kFormZ4U) * R) >= 0.9))) {
     ok = true; z.zu = kFormZ4U; z.zm = kFormZ4M; z.form = CTN_FORM_ZIPM64;
+  }
+  // bond 512 (k_zip512_f32: 64 values of u per workgroup; its tile depth divides ZK, so zip_match's K1 condition - a
+  // multiple of 16 and >= 32 - covers it), when no other form matches: only on request (CTN_ZIP=1, and not
+  // CTN_ZIP512=0).  kZip512Default as kZip128Default: the measurement that has to decide it is in DESIGN section 10.
+  if (!ok && sw.zip512 != 0 && sw.zip != 0 && sw.zip != 2 && zip_match(P, s, &z, CTN_F32, kFormZ5U, kFormZ5M) &&
+      ((z.ldE | z.ldXq | z.ldXk | z.ldYq | z.ldYm | z.ldC) & 3) == 0 &&
+      (sw.zip == 1 || (kZip512Default && (int64_t)(z.U / kFormZ5U) * R >= n_cu && fill((int64_t)(z.U / kFormZ5U) * R) >= 0.9))) {
+    ok = true; z.zu = kFormZ5U; z.zm = kFormZ5M; z.form = CTN_FORM_ZIP512;
   }
   if (!ok || z.U / z.zu > kMaxPartials) return false;    // (one abs-sum partial per workgroup: the consumers add at most that many)
   *out = z;

@@ -45,6 +45,8 @@ struct DevSwitches {
                          // |m1| = |n2| = 128 that no bond-256 form matches
   int zipm64 = 1;        // CTN_ZIPM64=0: never the bond-64 pair kernel (k_zipm64_f32), which CTN_ZIP=1 takes for fp32 pairs with
                          // |m1| = |n2| = 64 (no bond-256 and no bond-128 form matches those)
+  int zip512 = 1;        // CTN_ZIP512=0: never the bond-512 pair kernel (k_zip512_f32), which CTN_ZIP=1 takes for fp32 pairs with
+                         // |m1| = |n2| = 512 (no other form matches those)
   int cplx = -1;         // CTN_CPLX: 1 a complex x complex step pair - the S step and the 4-byte-gather GEMM behind it - runs as one launch
                          // (k_cmfma_f32) wherever cplx_match takes it; 0 or unset: never (kCplxDefault)
   int chain = -1;        // CTN_CHAIN: 1 a chain plan is always walked by k_chain, 2 by k_chain_lds (records, inputs and intermediates
@@ -82,6 +84,7 @@ inline DevSwitches read_dev_switches() {
   d.zipq_wgs = num("CTN_ZIPQ_WGS", 0);
   d.zip128 = num("CTN_ZIP128", 1);
   d.zipm64 = num("CTN_ZIPM64", 1);
+  d.zip512 = num("CTN_ZIP512", 1);
   d.zipl = num("CTN_ZIPL", -1);
   d.cplx = num("CTN_CPLX", -1);
   d.chain = num("CTN_CHAIN", -1);

@@ -170,9 +170,10 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                  never exists in memory reports 0.0 and the NEXT launched step carries the product of both:
  *                    - ctn_step_info.kernel == CTN_KERNEL_FUSED (formed inside its consumer);
  *                    - the first step of a zipper pair run as one launch, in every form of it - k_zip_f32,
- *                      k_zip64_f32, k_zip128_f32, k_zipm64_f32, k_zip_lat (fp32) and k_zip_f64 (fp64) -
+ *                      k_zip64_f32, k_zip128_f32, k_zipm64_f32, k_zip512_f32, k_zip_lat (fp32) and k_zip_f64 (fp64) -
  *                      (ctn_exec_step_tile reports (1, 1) for it, and for the second step the form's own tile:
- *                      (512, 256), (512, 128), (512, 64) for bond 128 and (256, 32) for bond 64, k_zipm64_f32):
+ *                      (512, 256), (512, 128), (512, 64) for bond 128, (256, 32) for bond 64, k_zipm64_f32, and
+ *                      (512, 512) for bond 512, k_zip512_f32 (CTN_ZIP=1; CTN_ZIP512=0 keeps it off)):
  *                      (T / s) Y = (T Y) / s, the second step's factor is s_T * s_E' of the
  *                      reference.  k_zip_lat's factors are BOUNDS: its result leaves as 256 / MP slabs and the pair
  *                      reports sum over slabs of sum |slab| / numel >= sum |E'| / numel (the true mean within the
@@ -282,7 +283,7 @@ int ctn_exec_merge_scales(ctn_exec* exec, int t_dtype, void* buf, int64_t stride
  * can be overridden at launch time by the number of replicas: few tiles -> 64 x 64 split-K or 128 x 64,
  * many full long-K tiles -> 256 x 256.  Measurement tooling only (bench.py keys its per-kernel roofline on it).
  * A step that runs inside the launch of a later one (see step_rescales above) reports (1, 1); the fused forms report
- * tiles no plain form has: the zipper pairs (512, 256), (512, 128), (512, 64), (256, 32), (32, 256), (64, 256 with
+ * tiles no plain form has: the zipper pairs (512, 256), (512, 128), (512, 64), (256, 32), (512, 512), (32, 256), (64, 256 with
  * (1, 1) before it); a sweep (16, D P); the complex pair k_cmfma_f32 (64, 256) behind the (1, 1) of its S step.
  * The fp64 latency form k_zip_lat_f64 reports (32, 256) behind the (1, 1) of its absorbed step, exactly as k_zip_lat does.
  */
@@ -304,7 +305,8 @@ typedef enum {
   CTN_FORM_ZIPM64 = 5,  /* k_zipm64_f32 */
   CTN_FORM_ZIP_F64 = 6, /* k_zip_f64 */
   CTN_FORM_ZIPQP = 7,   /* k_zipqp_f32: k_zipq_f32 with a workgroup that walks several work items of the launch */
-  CTN_FORM_ZIPL_F64 = 8 /* k_zip_lat_f64: the float64 latency form, tile (32, 256) (the fp32 latency form k_zip_lat reports NONE) */
+  CTN_FORM_ZIPL_F64 = 8, /* k_zip_lat_f64: the float64 latency form, tile (32, 256) (the fp32 latency form k_zip_lat reports NONE) */
+  CTN_FORM_ZIP512 = 9   /* k_zip512_f32: the bond-512 pair on 16 x 16 x 4 MFMAs, 64 values of u per workgroup, tile (512, 512) */
 } ctn_step_form;
 int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form);
 
