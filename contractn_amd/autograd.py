@@ -23,6 +23,11 @@ when the root of a split-format result was not rescaled.  Double backward is not
 `engine.GradTape`; include/ctn_abi.h, ctn_grad_tape_*) - the walk's launches in the walk's order over an arena the tape
 owns, issued by one native call and replayed as one hipGraph from its third run on; the same bits.  The default is the
 walk.  `backward_stats()` counts the backwards by path.
+
+``CTN_GRAD_CLOSE=1`` (read on every backward, independent of the tape): every one-step run goes out with its finish and
+its register work as one launch (k_run_close; `engine.Executor.enqueue_closed` in the walk, `engine.TAPE_CLOSE` on the
+tape's RUN records) instead of three - the same bits, two dispatches fewer per run.  The walk keeps the three calls where
+the rescale flags go to the host with the snapshot, and where the engine refuses.  `close_stats()` counts the runs.
 """
 import os
 import threading
@@ -207,10 +212,12 @@ class BackwardSchedule:
         return ex
 
     # -- the backward tape (CTN_GRAD_TAPE=1) ------------------------------------------------------------------------
-    def tape_records(self, need, frontier, grad_dtypes, has_gt=True, has_gc=True):
+    def tape_records(self, need, frontier, grad_dtypes, has_gt=True, has_gc=True, close=False):
         """The reverse pass of `_backward` as the record list of a backward tape (include/ctn_abi.h, ctn_grad_tape_*):
         the same traversal, emitting a record where `_backward` launches.  Covers the data-independent case, every step
-        rescaled.  ``grad_dtypes``: numpy dtype of every operand's gradient.
+        rescaled.  ``grad_dtypes``: numpy dtype of every operand's gradient.  ``close`` (``CTN_GRAD_CLOSE=1``): every RUN
+        record carries `engine.TAPE_CLOSE` in ``reserved`` - its finish and its register work are one launch; nothing else
+        differs.
 
         Returns a dict: ``records`` and ``slots`` as `engine.GradTape` takes them, ``plans``, ``n_regs``, ``n_ext`` and
         ``zero`` (operands whose gradient is exactly zero: no record writes it).  External slot ``j < n`` is operand
@@ -247,6 +254,8 @@ class BackwardSchedule:
         def run(plan, a, b, out, log, dst, kids):
             records.append({"kind": engine.TAPE_RUN, "plan": plan_index(plan), "in": [a] + ([b] if b is not None else []),
                             "out": out, "reg": [log, dst] + list(kids), "src_dtype": self.dtype})
+            if close:
+                records[-1]["reserved"] = engine.TAPE_CLOSE
 
         def leaf(src, g, dims, strides, first, dst_dtype, out):
             records.append({"kind": engine.TAPE_LEAF, "in": [src], "out": out, "reg": [g if g is not None else -1],
@@ -318,18 +327,19 @@ class BackwardSchedule:
         return {"records": records, "slots": slots, "plans": plans, "n_regs": 4 * n_ids + 1, "n_ext": 2 * n + 2,
                 "zero": zero}
 
-    def tape(self, need, grad_dtypes, has_gt, has_gc, device, stream):
-        """The cached backward tape of one (needs mask, gradient dtypes, which cotangents arrive, device, stream, thread)
+    def tape(self, need, grad_dtypes, has_gt, has_gc, device, stream, close=False):
+        """The cached backward tape of one (needs mask, gradient dtypes, which cotangents arrive, device, stream, thread,
+        whether its RUN records close)
         as ``(engine.GradTape, its description)``, or None where there is none: no RUN record, an arena past the cap
         (``CTN_GRAD_TAPE_MAX_BYTES``), or a device out of memory for the arena or the tape's executors - the caller walks
         step by step then."""
         key = (tuple(bool(x) for x in need[:self.n_inputs]), tuple(np.dtype(d).str for d in grad_dtypes), bool(has_gt),
-               bool(has_gc), device, stream, threading.get_ident())
+               bool(has_gc), device, stream, threading.get_ident(), bool(close))
         with self._lock:
             if key in self._tapes:
                 return self._tapes[key]
         frontier = self.frontier([True] * self.n_steps)
-        d = self.tape_records(need, frontier, grad_dtypes, has_gt, has_gc)
+        d = self.tape_records(need, frontier, grad_dtypes, has_gt, has_gc, close)
         hit = None
         if any(r["kind"] == engine.TAPE_RUN for r in d["records"]):
             try:
@@ -583,11 +593,36 @@ def reset_backward_stats():
     with _STATS_LOCK:
         for k in _STATS_KEYS:
             _STATS[k] = 0
+        for k in _CLOSE_KEYS:
+            _CLOSE_STATS[k] = 0
 
 
 def _count(key):
     with _STATS_LOCK:
         _STATS[key] += 1
+
+
+_CLOSE_KEYS = ("closed_runs", "plain_runs")
+_CLOSE_STATS = dict.fromkeys(_CLOSE_KEYS, 0)
+
+
+def close_stats():
+    """The one-step runs of the backwards since the last `reset_backward_stats`, walked or taped: ``closed_runs`` went
+    out with their finish and register work as one launch (``CTN_GRAD_CLOSE=1``: `engine.Executor.enqueue_closed`, a RUN
+    record with `engine.TAPE_CLOSE`), ``plain_runs`` with the three launches."""
+    with _STATS_LOCK:
+        return dict(_CLOSE_STATS)
+
+
+def _count_runs(closed, plain):
+    with _STATS_LOCK:
+        _CLOSE_STATS["closed_runs"] += closed
+        _CLOSE_STATS["plain_runs"] += plain
+
+
+def _close_requested():
+    """``CTN_GRAD_CLOSE=1``, read on every backward like ``CTN_GRAD_TAPE``."""
+    return os.environ.get("CTN_GRAD_CLOSE", "0") == "1"
 
 
 def _backward_tape(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c):
@@ -600,7 +635,8 @@ def _backward_tape(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c):
     devi = dev.index or 0
     np_of = {torch.float32: np.float32, torch.float64: np.float64}
     with torch.cuda.stream(side) if side is not None else _NullCtx():
-        hit = sch.tape(need, [np_of.get(d, np.float64) for d in in_dtypes], g_t is not None, g_c is not None, devi, stream)
+        hit = sch.tape(need, [np_of.get(d, np.float64) for d in in_dtypes], g_t is not None, g_c is not None, devi, stream,
+                       _close_requested())
         if hit is None:
             return None
         tape, desc = hit
@@ -630,6 +666,11 @@ def _backward_tape(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c):
         for key in ("eager", "captured", "replayed"):
             if after[key] > before[key]:
                 _count("tape_" + key)
+        if "run_counts" not in desc:        # (closing, plain) RUN records: counted once per tape
+            runs = [r for r in desc["records"] if r["kind"] == engine.TAPE_RUN]
+            closed = sum(1 for r in runs if r.get("reserved", 0) & engine.TAPE_CLOSE)
+            desc["run_counts"] = (closed, len(runs) - closed)
+        _count_runs(*desc["run_counts"])
     _rejoin(torch, dev, side, [t for t in grads if t is not None])
     return grads
 
@@ -674,6 +715,17 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
         def add(dst, own, kids):
             ex_any.add_scales(reg(dst), reg(own), 1, [(reg(k), i0) for k in kids])
 
+        close = _close_requested()
+        runs = [0, 0]               # closed, plain
+
+        def run_closed(ex, ins, out, log, dst, kids):
+            """CTN_GRAD_CLOSE=1: the run, its log register and its sum as ONE call; False where the engine refuses."""
+            if not close or not ex.enqueue_closed(ins, [out], base, log, dst, *(list(kids) + [-1, -1])[:2]):
+                runs[1] += 1
+                return False
+            runs[0] += 1
+            return True
+
         # 1. recompute Z_hat_k and z_k step by step (the root only where a split-format seed needs it)
         zhat = {i: ops[i] for i in range(n)}
         last = S if sch.split_format else S - 1
@@ -686,10 +738,16 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
             plan = sch.recompute_plan(k)
             ex = ex_any = sch.executor(plan, devi, stream)
             buf = torch.empty(plan.out_shape, dtype=tdt, device=dev)
-            ex.enqueue([zhat[a].data_ptr()] + ([zhat[b].data_ptr()] if b >= 0 else []), [buf.data_ptr()])
-            ex.snapshot_scales(reg(LOG + n + k), 1, flags_host.data_ptr() + 8 * k if flags_host is not None else 0)
+            ins = [zhat[a].data_ptr()] + ([zhat[b].data_ptr()] if b >= 0 else [])
+            kids = [Z + a] + ([Z + b] if b >= 0 else [])
             zhat[n + k] = buf
-            add(Z + n + k, LOG + n + k, [Z + a] + ([Z + b] if b >= 0 else []))
+            if flags_host is not None:          # the flags go to the host with the snapshot: the three calls stay
+                runs[1] += 1
+            elif run_closed(ex, ins, buf.data_ptr(), LOG + n + k, Z + n + k, kids):
+                continue
+            ex.enqueue(ins, [buf.data_ptr()])
+            ex.snapshot_scales(reg(LOG + n + k), 1, flags_host.data_ptr() + 8 * k if flags_host is not None else 0)
+            add(Z + n + k, LOG + n + k, kids)
         if ex_any is None:          # a one-step plain contraction: any executor of the stream runs the bookkeeping
             ex_any = sch.executor(sch.recompute_plan(0), devi, stream)
         if flags_host is not None:
@@ -735,10 +793,12 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
                     continue
                 ex = sch.executor(plan, devi, stream)
                 res = torch.empty(plan.out_shape, dtype=tdt, device=dev)
-                ex.enqueue([buf.data_ptr(), zhat[other].data_ptr()], [res.data_ptr()])
-                ex.snapshot_scales(reg(LOG + child), 1)
+                ins = [buf.data_ptr(), zhat[other].data_ptr()]
                 kids = [g if g is not None else ZERO] + ([Z + other] if below else [])
-                add(G + child, LOG + child, kids)
+                if not run_closed(ex, ins, res.data_ptr(), LOG + child, G + child, kids):
+                    ex.enqueue(ins, [res.data_ptr()])
+                    ex.snapshot_scales(reg(LOG + child), 1)
+                    add(G + child, LOG + child, kids)
                 cot[child] = (res, out_l, G + child)
             del buf
         # 3. the operands' gradients, in their own shapes and dtypes
@@ -757,6 +817,7 @@ def _backward(torch, sch, ops, in_dtypes, needs_input_grad, g_t, g_c, root_resca
                              _src_strides(labels, lab, sch), first,
                              np.float32 if in_dtypes[j] == torch.float32 else np.float64, out.data_ptr())
             grads[j] = out
+    _count_runs(*runs)
     if side is not None:
         cur = torch.cuda.current_stream(dev)
         cur.wait_stream(side)

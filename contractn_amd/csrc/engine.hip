@@ -1050,8 +1050,16 @@ static int launch_step(Exec* E, int s, GroupCollect* gc) {
   return t.end();
 }
 
-// the scales of every step, then the final division
-static int launch_finish(Exec* E) {
+// What a closing run adds to its finish (ctn_exec_enqueue_closed, a closing RUN record of a backward tape): the register
+// block and the indices k_tape_regs takes.
+struct RunClose { double* regs; int r_log, r_dst, k0, k1; };
+
+// An executor may close its run - k_run_close in place of k_scales, k_finalize and the register launches - only when the
+// launch has one step's partials to read, one replica's result to divide, and does divide it.
+static bool exec_may_close(const Exec* E) { return E->plan->n_steps == 1 && E->R == 1 && !E->defer_finish; }
+
+// the scales of every step, then the final division; `close`: both and the run's register work as one launch
+static int launch_finish(Exec* E, const RunClose* close = nullptr) {
   const Plan& P = *E->plan;
   const int R = E->R;
   FinalArgs f;
@@ -1065,7 +1073,15 @@ static int launch_finish(Exec* E) {
   int fb = (int)std::min<int64_t>((P.output().numel / (f.vec ? (P.dtype == CTN_F64 ? 2 : 4) : 1) + 255) / 256, 4096);
   if (fb < 1) fb = 1;
   const dim3 sg((P.n_steps + 3) / 4, R);
-  if (P.dtype == CTN_F32) {
+  if (close) {
+    if (!exec_may_close(E)) { g_err = "this executor may not close its run (one step, one replica, no deferred finish)"; return CTN_UNSUPPORTED; }
+    if (P.dtype == CTN_F32)
+      hipLaunchKernelGGL(k_run_close<float>, dim3(fb, 1), dim3(256), 0, E->stream, f, E->d_logs, close->regs, close->r_log,
+                         close->r_dst, close->k0, close->k1);
+    else
+      hipLaunchKernelGGL(k_run_close<double>, dim3(fb, 1), dim3(256), 0, E->stream, f, E->d_logs, close->regs, close->r_log,
+                         close->r_dst, close->k0, close->k1);
+  } else if (P.dtype == CTN_F32) {
     hipLaunchKernelGGL(k_scales<float>, sg, dim3(256), 0, E->stream, f, E->d_logs);
     hipLaunchKernelGGL(k_finalize<float>, dim3(fb, R), dim3(256), 0, E->stream, f, (const double*)E->d_logs);
   } else {
@@ -1076,7 +1092,7 @@ static int launch_finish(Exec* E) {
   return CTN_OK;
 }
 
-static int exec_launch_steps(Exec* E) {
+static int exec_launch_steps(Exec* E, const RunClose* close = nullptr) {
   const Plan& P = *E->plan;
   int rc = CTN_OK;
   if (P.chain && E->d_chain != nullptr) {
@@ -1109,7 +1125,7 @@ static int exec_launch_steps(Exec* E) {
     }
   }
   if (rc != CTN_OK) return rc;
-  rc = launch_finish(E);
+  rc = launch_finish(E, close);
   if (rc != CTN_OK) return rc;
   if (E->timing_runs < E->timing_slots) E->timing_runs++;
   return CTN_OK;
@@ -1121,8 +1137,9 @@ static int exec_launch_steps(Exec* E) {
 // 1.6 - 2.6 ms of wall time): from the third enqueue on the sequence is replayed as ONE hipGraph launch.
 // Event-timed enqueues, the single-launch chain walk, debug stamping and streams that are themselves being
 // captured stay eager.  CTN_GRAPH=0 disables.
-static int exec_launch_all(Exec* E) {
+static int exec_launch_all(Exec* E, const RunClose* close = nullptr) {
   const Plan& P = *E->plan;
+  if (close) return exec_launch_steps(E, close);   // a closing run has one step: never a graph of its own
   const bool timed = E->timing_runs < E->timing_slots;
   const bool chain = P.chain && E->d_chain != nullptr;
   if (!E->use_graph || timed || chain || P.n_steps < 4 || E->eager_rescale || E->sw.stamps) return exec_launch_steps(E);
@@ -1441,6 +1458,23 @@ int ctn_exec_enqueue(ctn_exec* exec, const void* const* dev_inputs, void* const*
   if (rc != CTN_OK) return rc;
   exec_new_run(E);
   return exec_launch_all(E);
+}
+
+int ctn_exec_enqueue_closed(ctn_exec* exec, const void* const* dev_inputs, void* const* dev_outs, double* regs, int r_log,
+                            int r_dst, int k0, int k1) {
+  if (!exec || !dev_inputs || !dev_outs || !regs || r_log < 0 || r_dst < 0) { g_err = "invalid argument to ctn_exec_enqueue_closed"; return CTN_INVALID_ARG; }
+  Exec* E = &exec->e;
+  if (!exec_may_close(E)) {                        // before anything is touched: the caller issues the plain calls instead
+    g_err = "ctn_exec_enqueue_closed: the executor needs a one-step plan, one replica and no deferred finish";
+    return CTN_UNSUPPORTED;
+  }
+  DeviceGuard dg(E->device);
+  HIPCHECK(dg.err);
+  int rc = exec_set_pointers(E, dev_inputs, dev_outs);
+  if (rc != CTN_OK) return rc;
+  exec_new_run(E);
+  const RunClose close{regs, r_log, r_dst, k0, k1};
+  return exec_launch_all(E, &close);
 }
 
 int ctn_exec_synchronize(ctn_exec* exec) {
@@ -1933,6 +1967,7 @@ struct ctn_grad_tape {
   bool warm = false;
   hipGraphExec_t graph_exec = nullptr;
   int64_t n_eager = 0, n_captured = 0, n_replayed = 0;
+  int64_t graph_nodes = 0;                   // nodes of the captured graph (hipGraphGetNodes at capture time), 0 before
   int64_t device_bytes = 0, create_us = 0;   // what creation took from the device (arena, table, executors) and how long
 
   ~ctn_grad_tape() {
@@ -1998,6 +2033,12 @@ static int tape_issue(ctn_grad_tape* T) {
     if (r.kind == CTN_TAPE_RUN) {
       Exec* E = &T->execs[i]->e;
       exec_new_run(E);
+      if (tape_closes(r)) {                        // the register work rides in the run's own finish (k_run_close)
+        const RunClose close{regs, r.reg[0], r.reg[1], r.reg[2], r.reg[3]};
+        const int rc = exec_launch_all(E, &close);
+        if (rc != CTN_OK) return rc;
+        continue;
+      }
       const int rc = exec_launch_all(E);
       if (rc != CTN_OK) return rc;
       hipLaunchKernelGGL(k_tape_regs, dim3(1), dim3(64), 0, st, (const double*)E->d_log, regs, r.reg[0], r.reg[1], r.reg[2], r.reg[3]);
@@ -2122,6 +2163,10 @@ int ctn_grad_tape_create(const ctn_tape_desc* desc, int device, void* stream, ct
     if (rc != CTN_OK) return fail(rc);
     ++T->n_execs;
     (void)ctn_exec_set_rescale_mode(T->execs[i], 1);       // eager: one-step runs are never "suspect", nothing to fetch
+    if (tape_closes(r) && !exec_may_close(&T->execs[i]->e)) {
+      g_err = "ctn_grad_tape_create: record " + std::to_string(i) + " closes, but its plan may not (one step, one replica)";
+      return fail(CTN_INVALID_ARG);
+    }
     const bool ext = T->slots[r.in[0]].external || (r.in[1] >= 0 && T->slots[r.in[1]].external);
     if (ext) { T->ext_runs.push_back((int)i); continue; }
     rc = tape_set_run_pointers(T, (int)i);                  // all in the arena: set once, before any capture
@@ -2187,6 +2232,9 @@ int ctn_grad_tape_run(ctn_grad_tape* T, void* const* ext, int n_ext) {
       ++T->n_eager;
       return tape_issue(T);
     }
+    size_t n_nodes = 0;
+    if (hipGraphGetNodes(g, nullptr, &n_nodes) == hipSuccess) T->graph_nodes = (int64_t)n_nodes;
+    else (void)hipGetLastError();
     (void)hipGraphDestroy(g);
     HIPCHECK(hipGraphLaunch(T->graph_exec, T->stream));
     ++T->n_captured;
@@ -2203,6 +2251,12 @@ int ctn_grad_tape_info(const ctn_grad_tape* T, int64_t* info) {
   info[3] = T->n_eager; info[4] = T->n_captured; info[5] = T->n_replayed;
   info[6] = T->regs_bytes; info[7] = (int64_t)T->slots.size();
   info[8] = T->device_bytes; info[9] = T->create_us;
+  return CTN_OK;
+}
+
+int ctn_grad_tape_graph_nodes(const ctn_grad_tape* T, int64_t* nodes) {
+  if (!T || !nodes) { g_err = "invalid argument to ctn_grad_tape_graph_nodes"; return CTN_INVALID_ARG; }
+  *nodes = T->graph_nodes;
   return CTN_OK;
 }
 

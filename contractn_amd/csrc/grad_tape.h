@@ -16,6 +16,10 @@ constexpr int64_t kTapeDefaultMaxBytes = (int64_t)1 << 30;
 
 inline int64_t tape_round_up(int64_t v) { return (v + kTapeAlign - 1) / kTapeAlign * kTapeAlign; }
 
+// Bit 0 of ctn_tape_record.reserved: this RUN record closes - its finish and its register work are one launch.
+constexpr int32_t kTapeClose = 1;
+inline bool tape_closes(const ctn_tape_record& r) { return (r.reserved & kTapeClose) != 0; }
+
 // The slots a record reads and the slots it writes (the seed's scratch is written and read inside the record).
 struct TapeAccess { int reads[3]; int n_reads = 0; int writes[2]; int n_writes = 0; };
 inline TapeAccess tape_access(const ctn_tape_record& r) {
@@ -60,6 +64,8 @@ inline std::string tape_check_records(const ctn_tape_desc& d, std::vector<TapeLi
     const std::string at = "record " + std::to_string(i) + ": ";
     if (r.kind != CTN_TAPE_RUN && r.kind != CTN_TAPE_SEED && r.kind != CTN_TAPE_LEAF) return at + "unknown kind";
     if (!tape_regs_ok(r, d.n_regs)) return at + "a register index leaves the block";
+    if (r.reserved & ~kTapeClose) return at + "unknown bits in reserved";
+    if (tape_closes(r) && r.kind != CTN_TAPE_RUN) return at + "only a RUN record closes";
     auto slot_ok = [&](int v) { return v >= 0 && v < d.n_slots; };
     if (!slot_ok(r.in[0]) || !slot_ok(r.out)) return at + "slot index out of range";
     for (int j = 1; j < 3; ++j)

@@ -186,4 +186,48 @@ __global__ __launch_bounds__(64) void k_tape_regs(const double* __restrict__ run
   regs[r_dst] = v;
 }
 
+// k_run_close: everything behind the step of a ONE-step, one-replica run in one launch (CTN_GRAD_CLOSE=1) - what k_scales,
+// k_finalize and k_tape_regs do in three.  Grid (fb, 1) as k_finalize's.  Every wave of every workgroup derives the step's
+// factor itself from the partials, with k_scales' own producer_scale call (a fixed order: the same bits everywhere), so
+// no workgroup reads what another one writes in this launch; then the workgroup divides its share of the result with
+// k_finalize's two loops.  Workgroup 0 also writes, from one lane, the run's factor and log (f.rescales[0], logs[0]),
+// its register f.log_scale[0] - block_sum of ONE term is 0.0 + term -, and the tape's registers as k_tape_regs does.
+// Never launched with f.defer set.
+template <typename T>
+__global__ __launch_bounds__(256) void k_run_close(FinalArgs f, double* __restrict__ logs, double* __restrict__ regs,
+                                                   int r_log, int r_dst, int k0, int k1) {
+  bool cond = false;
+  T sc = (T)1;
+  if (f.stabilize)
+    sc = producer_scale<T>(f.partials + (size_t)f.stepOff[0] * f.R, f.stepP[0], f.stepSlots[0], f.stepNumel[0],
+                           f.min_norm, 0, &cond);
+  const double rl = cond ? (double)sc : 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const double lg = cond ? (double)log(sc) : 0.0;
+    f.rescales[0] = rl;
+    logs[0] = lg;
+    double v = 0.0 + lg;
+    f.log_scale[0] = v;
+    regs[r_log] = v;
+    if (k0 >= 0) v += regs[k0];
+    if (k1 >= 0) v += regs[k1];
+    regs[r_dst] = v;
+  }
+  if (!f.stabilize) return;
+  if (rl == 0.0) return;  // the step was not rescaled (norm <= min_norm): tensor unchanged
+  const T s_last = (T)rl;
+  T* out = (T*)f.ptrs[f.id_out];
+  constexpr int V = 16 / (int)sizeof(T);
+  typedef T vecT __attribute__((ext_vector_type(V)));
+  const int64_t nv = f.vec ? f.out_numel / V : 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nv; i += (int64_t)gridDim.x * 256) {
+    vecT v = reinterpret_cast<vecT*>(out)[i];
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = v[j] / s_last;
+    reinterpret_cast<vecT*>(out)[i] = v;
+  }
+  for (int64_t i = nv * V + (int64_t)blockIdx.x * 256 + threadIdx.x; i < f.out_numel; i += (int64_t)gridDim.x * 256)
+    out[i] = out[i] / s_last;
+}
+
 }  // namespace ctn

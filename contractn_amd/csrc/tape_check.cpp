@@ -8,7 +8,8 @@
 //   tape <n_records> <n_slots> <n_ext> <n_regs> <given: 0 = lay the arena out with tape_layout | 1 = offsets are given |
 //                                                 2 = as 0, static checks only: a layout too large to replay word by word>
 //   slot <external 0|1> <ext_index> <bytes> <offset>            (n_slots lines; offset is read only when given = 1)
-//   rec <kind> <plan> <in0> <in1> <in2> <out> <aux> <reg0> <reg1> <reg2> <reg3>       (n_records lines)
+//   rec <kind> <plan> <in0> <in1> <in2> <out> <aux> <reg0> <reg1> <reg2> <reg3> [<reserved>]   (n_records lines; reserved:
+//                                                 bit 0 = a RUN record that closes, CTN_GRAD_CLOSE=1; left out = 0)
 //   arena <bytes>                                               (only when given = 1)
 //
 // Two things are checked for every tape, and both must pass:
@@ -171,6 +172,8 @@ std::string replay(const Tape& t) {
         const ctn_tape_record& r = t.recs[i];
         if (r.kind != CTN_TAPE_RUN && r.kind != CTN_TAPE_SEED && r.kind != CTN_TAPE_LEAF) throw Fail{"unknown kind"};
         if (r.kind == CTN_TAPE_SEED) a.slot_ok(r.aux);
+        // a closing RUN record leaves what a plain one and its k_tape_regs leave: eval() is the same for both
+        if (tape_closes(r) && r.kind != CTN_TAPE_RUN) throw Fail{"record " + std::to_string(i) + ": only a RUN record closes"};
         try {
           eval(r, b);
           eval(r, a);
@@ -222,6 +225,11 @@ int main() {
       r = ctn_tape_record{};
       std::cin >> word >> r.kind >> r.plan >> r.in[0] >> r.in[1] >> r.in[2] >> r.out >> r.aux >> r.reg[0] >> r.reg[1] >> r.reg[2] >> r.reg[3];
       if (!std::cin || word != "rec") { printf("parse error at record %d\n", i); return 2; }
+      while (std::cin.peek() == ' ' || std::cin.peek() == '\t') std::cin.get();
+      if (std::cin.peek() >= '0' && std::cin.peek() <= '9') {          // the optional twelfth field
+        std::cin >> r.reserved;
+        if (!std::cin) { printf("parse error at record %d\n", i); return 2; }
+      }
       r.numel = 1;
       max_plan = std::max(max_plan, r.plan);
     }

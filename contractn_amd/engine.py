@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "ctn_grad_seed", "ctn_grad_leaf",
     "ctn_cplx_normalize", "ctn_cplx_normalize_grad",
     "ctn_grad_tape_create", "ctn_grad_tape_run", "ctn_grad_tape_info", "ctn_grad_tape_destroy",
+    "ctn_exec_enqueue_closed", "ctn_grad_tape_graph_nodes",
 )
 # ctn_step_form (ctn_exec_step_form): the fused zipper-pair kernel a step ran as
 STEP_FORMS = {0: None, 1: "k_zip_f32", 2: "k_zipq_f32", 3: "k_zip64_f32", 4: "k_zip128_f32", 5: "k_zipm64_f32", 6: "k_zip_f64", 7: "k_zipqp_f32",
@@ -54,6 +55,7 @@ GRAD_SCRATCH = 512          # doubles of scratch ctn_grad_seed needs (CTN_GRAD_S
 GRAD_MAX_DIMS = 64          # axes of an operand ctn_grad_leaf writes (CTN_GRAD_MAX_DIMS)
 CPLX_SCRATCH = 1024         # doubles of scratch ctn_cplx_normalize(_grad) needs (CTN_CPLX_SCRATCH)
 TAPE_RUN, TAPE_SEED, TAPE_LEAF = 0, 1, 2     # ctn_tape_kind
+TAPE_CLOSE = 1              # ctn_tape_record.reserved, bit 0: a RUN record whose finish and register work are one launch
 TAPE_MAX_BYTES = 1 << 30    # default cap of a backward tape's arena (CTN_GRAD_TAPE_MAX_BYTES overrides)
 TAPE_INFO = ("records", "arena_bytes", "executors", "eager", "captured", "replayed", "regs_bytes", "slots",
              "device_bytes", "create_us")
@@ -213,6 +215,8 @@ def load_library():
         "ctn_grad_tape_run": (i32, [vp, C.POINTER(vp), i32]),
         "ctn_grad_tape_info": (i32, [vp, C.POINTER(C.c_int64)]),
         "ctn_grad_tape_destroy": (None, [vp]),
+        "ctn_exec_enqueue_closed": (i32, [vp, C.POINTER(vp), C.POINTER(vp), vp, i32, i32, i32, i32]),
+        "ctn_grad_tape_graph_nodes": (i32, [vp, C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -458,6 +462,23 @@ class Executor:
         op = (C.c_void_p * R)(*out_ptrs)
         _check(self._lib.ctn_exec_enqueue(self._h, ip, op))
 
+    def enqueue_closed(self, in_ptrs, out_ptrs, regs_ptr, r_log, r_dst, k0=-1, k1=-1):
+        """`enqueue` of a one-step plan with the run's register work in its closing launch (include/ctn_abi.h,
+        ctn_exec_enqueue_closed): ``regs[r_log]`` = the run's log register, ``regs[r_dst] = regs[r_log] + regs[k0] +
+        regs[k1]`` (``k < 0``: no such term) - what `snapshot_scales` and `add_scales` leave, the same bits.  ``regs_ptr``:
+        device address of a float64 block.  Returns False, with nothing launched, where the executor may not close (more
+        than one step or replica, deferred finish): the caller makes the three calls then."""
+        plan, R = self.plan, self.replicas
+        assert len(in_ptrs) == R * plan.n_inputs and len(out_ptrs) == R
+        ip = (C.c_void_p * len(in_ptrs))(*in_ptrs)
+        op = (C.c_void_p * R)(*out_ptrs)
+        rc = self._lib.ctn_exec_enqueue_closed(self._h, ip, op, C.c_void_p(regs_ptr), int(r_log), int(r_dst), int(k0),
+                                               int(k1))
+        if rc == -3:
+            return False
+        _check(rc)
+        return True
+
     def make_enqueue(self, in_ptrs, out_ptrs):
         """Pre-marshal the pointer arrays once; returns a zero-argument launcher."""
         plan, R = self.plan, self.replicas
@@ -640,8 +661,8 @@ class GradTape:
 
     ``records``: dicts with the fields of ``ctn_tape_record`` (``kind``, ``plan`` - an index into ``plans`` -, ``in`` (up to
     three slots), ``out``, ``aux``, ``reg`` (up to four registers), ``src_dtype`` / ``dst_dtype`` as numpy dtypes, and for
-    a LEAF ``dims`` / ``strides`` / ``first``, for a SEED ``numel`` / ``min_norm``); ``slots``: ``(external, ext_index,
-    bytes)``.  One thread at a time, like an `Executor`."""
+    a LEAF ``dims`` / ``strides`` / ``first``, for a SEED ``numel`` / ``min_norm``, for a RUN that closes ``reserved`` =
+    `TAPE_CLOSE`); ``slots``: ``(external, ext_index, bytes)``.  One thread at a time, like an `Executor`."""
 
     def __init__(self, records, slots, n_ext, n_regs, plans, device, stream, max_bytes=None):
         lib = load_library()
@@ -674,6 +695,13 @@ class GradTape:
         _check(self._lib.ctn_grad_tape_info(self._h, out))
         return dict(zip(TAPE_INFO, (int(v) for v in out)))
 
+    def graph_nodes(self):
+        """Nodes of the captured graph (counted when the capture ended); 0 before the capture and for a tape that stays
+        eager.  A closing RUN record (``reserved`` bit 0) has two nodes fewer than a plain one."""
+        out = C.c_int64(0)
+        _check(self._lib.ctn_grad_tape_graph_nodes(self._h, C.byref(out)))
+        return int(out.value)
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -705,6 +733,7 @@ def tape_desc(records, slots, n_ext, n_regs, plans, max_bytes=None):
         strides += list(src.get("strides", ()))
         first += list(src.get("first", ()))
         r.numel, r.min_norm = int(src.get("numel", 0)), float(src.get("min_norm", 0.0))
+        r.reserved = int(src.get("reserved", 0))
     sl = (TapeSlot * max(len(slots), 1))()
     for dst, (ext, idx, nbytes) in zip(sl, slots):
         dst.external, dst.ext_index, dst.bytes = int(ext), int(idx), int(nbytes)

@@ -198,6 +198,15 @@ int ctn_exec_run(ctn_exec* exec, const void* const* inputs, int inputs_space,
 
 /* Asynchronous variant: device pointers only, returns after enqueueing on the stream. */
 int ctn_exec_enqueue(ctn_exec* exec, const void* const* dev_inputs, void* const* dev_outs);
+/* ctn_exec_enqueue of a ONE-step plan with the run's register work in the same launch as its finish (k_run_close: what
+ * k_scales, k_finalize and the two bookkeeping launches do, the same bits):  regs[r_log] = the run's log register and
+ * regs[r_dst] = regs[r_log] + regs[k0] + regs[k1], added in that order (k < 0: no such term) - what
+ * ctn_exec_snapshot_scales(exec, regs + r_log, 1, NULL) and ctn_exec_add_scales on the two terms leave.  `regs`: a block of
+ * float64 device registers.  The executor's own registers (ctn_exec_fetch) are written as always.
+ * CTN_UNSUPPORTED, with nothing launched and nothing touched, unless the plan has exactly one step, the executor one
+ * replica, and finish mode 0: the caller issues the three calls instead.  (The entry point leaves CTN_ABI_VERSION as it is.) */
+int ctn_exec_enqueue_closed(ctn_exec* exec, const void* const* dev_inputs, void* const* dev_outs, double* regs, int r_log,
+                            int r_dst, int k0, int k1);
 /* Wait for the stream and copy out the scale registers of the last enqueue (either may be NULL).
  * The operands and outputs of that enqueue stay borrowed until this call returns: when the scale registers
  * show that a lazily rescaled product left the dtype's range (see ctn_exec_set_rescale_mode) the contraction is
@@ -401,6 +410,9 @@ int ctn_cplx_normalize_grad(ctn_exec* exec, int dtype, const void* t, const void
  *   CTN_TAPE_RUN   enqueue one-step plan `plan` (eager rescale mode, an executor of its own) on in[0], in[1] (-1: unary)
  *                  into `out`; then reg[0] = the run's log register and reg[1] = reg[0] + reg[2] + reg[3], added in
  *                  that order (what ctn_exec_snapshot_scales and ctn_exec_add_scales do, as one launch of k_tape_regs).
+ *                  Bit 0 of `reserved` set: the record CLOSES - the run is issued as ctn_exec_enqueue_closed issues it,
+ *                  its finish and this register work one launch (k_run_close), and no k_tape_regs follows; the same bits.
+ *                  The bit is refused (CTN_INVALID_ARG) on SEED and LEAF records, as is any other bit of `reserved`.
  *   CTN_TAPE_SEED  ctn_grad_seed: t_hat = in[0], g_hat = in[1], g_c = in[2], scratch = aux (an arena slot of
  *                  CTN_GRAD_SCRATCH doubles), z = reg[0], g_in = reg[1], g_out = reg[2]; numel, min_norm; dtype = src_dtype.
  *   CTN_TAPE_LEAF  ctn_grad_leaf: src = in[0], g = reg[0], dst = out; ndim axes described by entries
@@ -421,6 +433,8 @@ int ctn_cplx_normalize_grad(ctn_exec* exec, int dtype, const void* t, const void
  * ctn_grad_tape_info: info[0..10) = records, arena bytes, executors, eager runs, captured runs, replayed runs,
  *   bytes of the register block, slots, device bytes the creation took (arena, table and executors together, as the
  *   free memory of the device fell), microseconds the creation took.
+ * ctn_grad_tape_graph_nodes: *nodes = the node count of the captured graph (hipGraphGetNodes when the capture ended), 0
+ *   before a capture and for a tape that stays eager.  A closing RUN record has two nodes fewer than a plain one.
  */
 typedef enum { CTN_TAPE_RUN = 0, CTN_TAPE_SEED = 1, CTN_TAPE_LEAF = 2 } ctn_tape_kind;
 typedef struct {
@@ -434,7 +448,7 @@ typedef struct {
   int32_t dst_dtype;
   int32_t ndim;
   int32_t axes;
-  int32_t reserved;
+  int32_t reserved;  /* bit 0: a RUN record closes (above); every other bit 0 */
   int64_t numel;
   double min_norm;
 } ctn_tape_record;
@@ -458,6 +472,7 @@ typedef struct ctn_grad_tape ctn_grad_tape;
 int ctn_grad_tape_create(const ctn_tape_desc* desc, int device, void* stream, ctn_grad_tape** out);
 int ctn_grad_tape_run(ctn_grad_tape* tape, void* const* ext, int n_ext);
 int ctn_grad_tape_info(const ctn_grad_tape* tape, int64_t* info /* [CTN_TAPE_INFO] */);
+int ctn_grad_tape_graph_nodes(const ctn_grad_tape* tape, int64_t* nodes);
 void ctn_grad_tape_destroy(ctn_grad_tape* tape);
 
 #ifdef __cplusplus

@@ -1,7 +1,8 @@
 """Backward cost of contract() on device tensors (contractn_amd/autograd.py), one MI355X.
 
-    python tools/grad_bench.py [--reps 5] [--warmup 2] [--tape {0,1}] [--dtypes float32,float64] [--only NAME]
+    python tools/grad_bench.py [--reps 5] [--warmup 2] [--tape {0,1}] [--close {0,1}] [--dtypes float32,float64] [--only NAME]
     python tools/grad_bench.py --ab 5            # walk and backward tape alternated in one session, median and spread
+    python tools/grad_bench.py --ab 5 --close 1  # the tape and the closing tape (CTN_GRAD_CLOSE=1) alternated likewise
     python tools/grad_bench.py --tape 1 --only mps100_D256 --profile-iters 20      # under a kernel trace: K steps, no timing
 
 Per network: the no-grad forward, then forward + backward of a loss on ``(T_hat, c)``, both timed with torch events on
@@ -16,7 +17,10 @@ One JSON line per network and dtype (``--dtypes``: every network cast to each; d
 backward as a backward tape (CTN_GRAD_TAPE=1: one native call, a graph replay from the third run on).  ``--ab N`` times
 forward + backward N times under each setting in turn - walk, tape, walk, ... - and reports per setting the median of
 the N medians and their spread (max - min); the warm-up of the first round carries the tape past its capture.  Both
-report under ``tapes`` what the tapes cost to create (executors, device bytes, milliseconds).
+report under ``tapes`` what the tapes cost to create (executors, device bytes, milliseconds).  ``--close 1`` sets
+CTN_GRAD_CLOSE=1 (every one-step run of the backward closes in one launch, k_run_close); with ``--ab N`` the two settings
+alternated are then the tape and the tape with closing runs, each with a tape of its own, and ``graph_nodes`` lists the
+nodes of the captured graphs.
 """
 import argparse
 import json
@@ -54,7 +58,8 @@ def tape_cost(AG):
         for hit in list(sch._tapes.values()):
             if hit is not None:
                 i = hit[0].info()
-                out.append({"records": i["records"], "executors": i["executors"], "arena_bytes": i["arena_bytes"],
+                out.append({"records": i["records"], "executors": i["executors"], "graph_nodes": hit[0].graph_nodes(),
+                            "arena_bytes": i["arena_bytes"],
                             "device_bytes": i["device_bytes"], "create_ms": round(i["create_us"] / 1e3, 1)})
     return out
 
@@ -82,13 +87,17 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tape", type=int, choices=(0, 1), default=None, help="CTN_GRAD_TAPE for the backward (default: as set)")
+    ap.add_argument("--close", type=int, choices=(0, 1), default=None, help="CTN_GRAD_CLOSE for the backward (default: as set)")
     ap.add_argument("--dtypes", default="", help="comma-separated dtypes every network is cast to (default: its own)")
     ap.add_argument("--only", default="", help="run this network only")
-    ap.add_argument("--ab", type=int, default=0, help="alternate walk and tape this many times, report median and spread")
+    ap.add_argument("--ab", type=int, default=0, help="alternate walk and tape (--close 1: tape and closing tape) this many times, "
+                                                      "report median and spread")
     ap.add_argument("--profile-iters", type=int, default=0, help="just this many forward + backward steps, nothing timed")
     args = ap.parse_args()
     if args.tape is not None:
         os.environ["CTN_GRAD_TAPE"] = str(args.tape)
+    if args.close is not None:
+        os.environ["CTN_GRAD_CLOSE"] = str(args.close)
     import torch
 
     from contractn_amd import autograd as AG
@@ -131,17 +140,20 @@ def main():
             continue
         if args.ab:
             t_f = timed(torch, fwd, args.reps, args.warmup)
-            rounds = {"walk": [], "tape": []}
+            # setting -> (CTN_GRAD_TAPE, CTN_GRAD_CLOSE)
+            settings = {"tape": ("1", "0"), "tape_close": ("1", "1")} if args.close else {"walk": ("0", "0"), "tape": ("1", "0")}
+            rounds = {mode: [] for mode in settings}
             AG.reset_backward_stats()
             for i in range(args.ab):
-                for mode in ("walk", "tape"):
-                    os.environ["CTN_GRAD_TAPE"] = "1" if mode == "tape" else "0"
+                for mode, (tape, close) in settings.items():
+                    os.environ["CTN_GRAD_TAPE"], os.environ["CTN_GRAD_CLOSE"] = tape, close
                     rounds[mode].append(timed(torch, fwd_bwd, args.reps, max(args.warmup, 3) if i == 0 else 1))
             out = {"network": name, "dtype": dt, "forward_ms": round(t_f, 3), "reps": args.reps, "rounds": args.ab}
             for mode, ts in rounds.items():
                 out[mode] = {"median_ms": round(float(np.median(ts)), 3), "spread_ms": round(max(ts) - min(ts), 3),
                              "ratio": round(float(np.median(ts)) / t_f, 2), "rounds_ms": [round(t, 3) for t in ts]}
             out["backward"] = AG.backward_stats()
+            out["runs"] = AG.close_stats()
             out["tapes"] = tape_cost(AG)
             print(json.dumps(out), flush=True)
             continue
