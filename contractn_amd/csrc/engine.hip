@@ -47,8 +47,7 @@
 #include "kernels_zipq.h"
 #include "kernels_zipqp.h"
 #include "kernels_zip64.h"
-#include "kernels_zip128.h"
-#include "kernels_zipm64.h"
+#include "kernels_zipm.h"
 #include "kernels_zip512.h"
 #include "kernels_zip_f64.h"
 #include "kernels_zipl.h"
@@ -665,9 +664,9 @@ static void launch_renorm(Exec* E, int s) {
 // The zipper-pair kernels by ctn_step_form: threads per workgroup, the tile ctn_exec_step_tile reports, and whether a
 // workgroup walks the launch's work items (grid from zipq_grid; else one workgroup per `zu` values of u and replica).
 // The tile is 128 (or 64) values of u x all 256 n2 per workgroup; k_zip_f64 (64 values of u) reports (512, 256): an fp64
-// step with 128 tile columns reads as k_mfma_f64_g.  k_zip128_f32 (bond 128) reports (512, 64): the 64 values of m1 a
-// wave sums; k_zipm64_f32 (bond 64) likewise (256, 32): its 256 threads, 32 values of m1 per wave - a tile no plain
-// form reports (theirs are 16 x 16 or have 64 columns at least).  k_zip512_f32 (bond 512) reports (512, 512): its 512
+// step with 128 tile columns reads as k_mfma_f64_g.  The two instantiations of k_zipm_f32 (kernels_zipm.h): k_zip128_f32
+// (bond 128) reports (512, 64): the 64 values of m1 a wave sums; k_zipm64_f32 (bond 64) likewise (256, 32): its 256
+// threads, 32 values of m1 per wave - a tile no plain form reports (theirs are 16 x 16 or have 64 columns at least).  k_zip512_f32 (bond 512) reports (512, 512): its 512
 // threads and all 512 n2 - plain tiles have at most 256 rows, and no other pair kernel has 512 columns.  (Index 8,
 // CTN_FORM_ZIPL_F64, is the float64 latency form: it has a launcher of its own and no row here.)
 struct ZipKernel { void (*kernel)(ZipArgs); int threads, tm, tn; bool walks; };

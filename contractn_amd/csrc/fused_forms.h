@@ -19,7 +19,7 @@ namespace ctn {
 
 // What the rules below know of the kernels (engine.hip asserts that these are the kernels' own values): the zipper-pair
 // kernels' |m1| = |n2|, values of u per workgroup and phase-1 tile depth (ZM, ZU, ZK of kernels_zip.h; ZD*: kernels_zip_f64.h,
-// Z6*: kernels_zip64.h, Z1*: kernels_zip128.h, Z4*: kernels_zipm64.h, Z5*: kernels_zip512.h), the sweeps' inputs per workgroup and most sites
+// Z6*: kernels_zip64.h, Z1* and Z4*: kernels_zipm.h, Z5*: kernels_zip512.h), the sweeps' inputs per workgroup and most sites
 // (SWR, kSweepMaxSites of kernels_sweep.h), and the resident-operand kernel's M, K and column tile (AR_M, AR_K, AR_TN of
 // kernels_mfma_ares.h)
 constexpr int kFormZM = 256, kFormZU = 128, kFormZK = 16;

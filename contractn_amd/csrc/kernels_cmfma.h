@@ -209,9 +209,7 @@ __global__ __launch_bounds__(256, 2) void k_cmfma_f32(CplxArgs a) {
 
   const int tid = threadIdx.x;
   // XCD-aware remap, as k_mfma_f32: each XCD gets a contiguous range of tiles
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int r = pid / a.blocks_per_replica;
   const int t = pid - r * a.blocks_per_replica;
   const int m0 = (t / a.tiles_y) * CX_TX;

@@ -2,6 +2,7 @@
 // Part of the gfx950 contraction engine (see engine.hip for the overview).
 #pragma once
 #include "kernel_args.h"
+#include "zipq_items.h"   // zipq_pid(): the XCD remap of a block id, for every kernel that remaps
 #ifndef CTN_EXP
 #define CTN_EXP 0
 #endif
@@ -422,9 +423,7 @@ __global__ __launch_bounds__(256, (BK == 16 ? 3 : 2)) void k_mfma_f32(StepArgs a
   const int tid = threadIdx.x;
   // XCD-aware remap: workgroups are dealt round-robin over the 8 XCDs, so give each
   // XCD a contiguous range of tiles (one replica's tiles share that XCD's L2).
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int r = pid / a.blocks_per_replica;
   const int t = pid - r * a.blocks_per_replica;
   const int tiles_mn = a.tiles_m * a.tiles_n;
@@ -950,9 +949,7 @@ __global__ __launch_bounds__(256, 2) void k_mfma_f64(StepArgs a) {
   double* red = smem + 2 * SZA + 2 * SZB;
 
   const int tid = threadIdx.x;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int r = pid / a.blocks_per_replica;
   const int t = pid - r * a.blocks_per_replica;
   const int tiles_mn = a.tiles_m * a.tiles_n;

@@ -88,9 +88,7 @@ __global__ __launch_bounds__(512, 1) void k_mfma_f32_ares(StepArgs a, int ntw) {
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, h = lane >> 5;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int per = (a.N / AR_TN) / ntw;          // workgroups per batch entry
   const int perR = per * a.Bt;                  // ... per replica
   const int r = pid / perR;

@@ -43,9 +43,7 @@ __global__ __launch_bounds__(512, 1) void k_mfma_f32_h(StepArgs a) {
   const int kh = w >> 2, wq = w & 3;
   const int wm = (wq >> 1) * 64, wn = (wq & 1) * 64;
   const int l31 = lane & 31, h = lane >> 5;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int r = pid / a.blocks_per_replica;
   const int t = pid - r * a.blocks_per_replica;
   const int tiles_mn = a.tiles_m * a.tiles_n;

@@ -54,6 +54,14 @@ struct ZipArgs {
   int32_t n_items;          // R U / 128: the work items k_zipqp_f32's workgroups walk (the other kernels: one per workgroup, unread)
 };
 
+// One stamp of a workgroup's timeline: slot `k` of its 8 (a kernel with `a`, `tid` and `pid` in scope).  Nothing in a
+// build without CTN_STAMPS.
+#ifdef CTN_STAMPS
+#define CTN_ZIP_STAMP(k) do { if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define CTN_ZIP_STAMP(k) do { } while (0)
+#endif
+
 constexpr int ZM = 256, ZU = 128, ZK = 16, ZSTG = 8192;   // stage: 8192 floats = 32 KiB
 constexpr int ZST = 3;     // ring depth (4 measured: the requests are never waited for - 768 cycles per workgroup - nothing to gain)
 
@@ -66,16 +74,12 @@ __global__ __launch_bounds__(512, 1) void k_zip_f32(ZipArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kh = w >> 2, ub = w & 3;
   const int l31 = lane & 31, h = lane >> 5;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int per = a.U / ZU;                    // workgroups per replica
   const int r = pid / per;
   const int t_ = pid - r * per;
   const int u0 = t_ * ZU;
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 0] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(0);
   void* const* tp = a.ptrs + (size_t)r * a.n_tensors;
   const float* __restrict__ E = (const float*)tp[a.idE];
   const float* __restrict__ X = (const float*)tp[a.idX] + u0;
@@ -154,9 +158,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_f32(ZipArgs a) {
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): once per 134 MFLOP - no need to count
   __builtin_amdgcn_s_barrier();
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 1] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(1);
 
   // (measured without gain, LAB_NOTES R3: s_setprio 1 for waves 4-7; those waves taking the barrier at the END of a
   // tile so that the two waves of a SIMD run half a tile apart: -0.8 %)
@@ -306,9 +308,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_f32(ZipArgs a) {
         }
       }
   }
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 4] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(4);
 
   // ---- epilogue: lazy rescale by E's producer (X, Y are inputs), 16-byte stores, abs-sum partial ---------------
   pve = lane < a.PE ? pve : 0.0;
@@ -342,9 +342,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_f32(ZipArgs a) {
     for (int i = 0; i < 8; ++i) tot += red[i];
     a.partC[(size_t)r * a.partC_stride + t_] = tot;
   }
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 3] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(3);
 }
 
 }  // namespace ctn

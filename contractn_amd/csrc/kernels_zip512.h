@@ -85,16 +85,12 @@ __global__ __launch_bounds__(512, 1) void k_zip512_f32(ZipArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kh = w >> 2, ub = w & 3;
   const int l15 = lane & 15, h = lane >> 4;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int per = a.U / Z5U;                   // workgroups per replica
   const int r = pid / per;
   const int t_ = pid - r * per;
   const int u0 = t_ * Z5U;
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 0] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(0);
   void* const* tp = a.ptrs + (size_t)r * a.n_tensors;
   const float* __restrict__ E = (const float*)tp[a.idE];
   const float* __restrict__ X = (const float*)tp[a.idX] + u0;
@@ -171,9 +167,7 @@ __global__ __launch_bounds__(512, 1) void k_zip512_f32(ZipArgs a) {
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): once per pair - no need to count
   __builtin_amdgcn_s_barrier();
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 1] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(1);
 
   int st_cur = 0, st_nxt = 1, st_req = Z5ST - 1;
 #ifdef CTN_STAMPS
@@ -308,9 +302,7 @@ __global__ __launch_bounds__(512, 1) void k_zip512_f32(ZipArgs a) {
       }
     }
   }
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 4] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(4);
 
   // ---- epilogue: lazy rescale by E's producer (X, Y are inputs), 16-byte stores, abs-sum partial ---------------
   pve = lane_e < a.PE ? pve : 0.0;
@@ -345,9 +337,7 @@ __global__ __launch_bounds__(512, 1) void k_zip512_f32(ZipArgs a) {
     for (int i = 0; i < 8; ++i) tot += red[i];
     a.partC[(size_t)r * a.partC_stride + t_] = tot;
   }
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 3] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(3);
 }
 
 }  // namespace ctn

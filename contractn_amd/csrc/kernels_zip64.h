@@ -35,9 +35,7 @@ __global__ __launch_bounds__(512, 1) void k_zip64_f32(ZipArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kh = w >> 1, ub = w & 1;            // quarter of m1 (64 values), u-block of 32
   const int l31 = lane & 31, h = lane >> 5;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int per = a.U / Z6U;                    // workgroups per replica
   const int r = pid / per;
   const int t_ = pid - r * per;

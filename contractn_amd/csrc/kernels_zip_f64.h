@@ -61,16 +61,12 @@ __global__ __launch_bounds__(512, 1) void k_zip_f64(ZipArgs a) {
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kh = w >> 2, ub = w & 3;
   const int l15 = lane & 15, h = lane >> 4;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int per = a.U / ZDU;                   // workgroups per replica
   const int r = pid / per;
   const int t_ = pid - r * per;
   const int u0 = t_ * ZDU;
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 0] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(0);
   void* const* tp = a.ptrs + (size_t)r * a.n_tensors;
   const double* __restrict__ E = (const double*)tp[a.idE];
   const double* __restrict__ X = (const double*)tp[a.idX] + u0;
@@ -146,9 +142,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_f64(ZipArgs a) {
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): once per pair - no need to count
   __builtin_amdgcn_s_barrier();
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 1] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(1);
 
   int st_cur = 0, st_nxt = 1, st_req = ZDST - 1, t = 0;
 #ifdef CTN_STAMPS
@@ -274,9 +268,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_f64(ZipArgs a) {
         }
     }
   }
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 4] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(4);
 
   // ---- epilogue: lazy rescale by E's producer (X, Y are inputs), 16-byte stores, abs-sum partial ---------------
   pve = lane < a.PE ? pve : 0.0;
@@ -308,9 +300,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_f64(ZipArgs a) {
     for (int i = 0; i < 8; ++i) tot += red[i];
     a.partC[(size_t)r * a.partC_stride + t_] = tot;
   }
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 3] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(3);
 }
 
 }  // namespace ctn

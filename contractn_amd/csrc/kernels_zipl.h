@@ -69,12 +69,6 @@ struct ZipLatArgs {
   unsigned long long* dbg;  // CTN_STAMPS builds only
 };
 
-#ifdef CTN_STAMPS
-#define ZL_STAMP(k) do { if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define ZL_STAMP(k) do { } while (0)
-#endif
-
 typedef float zl_f4 __attribute__((ext_vector_type(4)));
 typedef float zl_f2 __attribute__((ext_vector_type(2)));
 
@@ -117,16 +111,14 @@ __global__ __launch_bounds__(512, 1) void k_zip_lat(ZipLatArgs a) {
   const int i16 = lane & 15, g = lane >> 4;
   // every XCD a contiguous range of work items; items are ordered (m1 part, replica, u block), so the workgroups of an
   // XCD share their E piece and their rows of Y through its L2
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int nub = a.U / 16, per_mp = a.R * nub;
   const int mp = pid / per_mp;
   const int rem = pid - mp * per_mp;
   const int r = rem / nub;
   const int ub = rem - r * nub;
   const int u0 = 16 * ub;
-  ZL_STAMP(0);
+  CTN_ZIP_STAMP(0);
 
   void* const* tp = a.ptrs + (size_t)r * a.n_tensors;
   const bool from_slabs = a.slabs_in != nullptr;
@@ -181,7 +173,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_lat(ZipLatArgs a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) yv[blk][e] = *reinterpret_cast<const zl_f2*>(py + (int64_t)e * a.ldYm);
   };
-  ZL_STAMP(1);
+  CTN_ZIP_STAMP(1);
 
   // ---- phase 1: T_block[m1 = 16 hh + i][u] += sum over this wave's k1 of E[k1][m1] Xq[k1][u], all NBQ blocks of its q.
   // The parts of k1 become available one after the other (slab sums -> LDS -> barrier); the waves of part kp start as soon
@@ -219,7 +211,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_lat(ZipLatArgs a) {
           acc1[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(cA[4 * s * LDE + 16 * b], xb[s], acc1[b], 0, 0, 0);
     }
   }
-  ZL_STAMP(2);
+  CTN_ZIP_STAMP(2);
   // D[i = m1][j = u] leaves lane (u, g) with m1 = 4 g + e in register e: one 16-byte store per block into [kp][blk][u][m1]
 #pragma unroll
   for (int b = 0; b < NBQ; ++b) {
@@ -228,9 +220,9 @@ __global__ __launch_bounds__(512, 1) void k_zip_lat(ZipLatArgs a) {
   }
 #pragma unroll
   for (int blk = NY0; blk < NBLK; ++blk) yrequest(blk);
-  ZL_STAMP(3);
+  CTN_ZIP_STAMP(3);
   zl_lds_barrier();
-  ZL_STAMP(4);
+  CTN_ZIP_STAMP(4);
 
   // ---- phase 2: E'^T[n2][u] = sum over the blocks of Y[q'][m1][n2] T[m1][q'][u] for this wave's 32 columns: the B operand
   // of a k-step pairs lane group g with m1 = 4 g + e - 16-byte LDS reads, the parts of k1 added in their order - and Y
@@ -246,7 +238,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_lat(ZipLatArgs a) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) acc2[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(yv[blk][e][t], tv[e], acc2[t], 0, 0, 0);
   }
-  ZL_STAMP(5);
+  CTN_ZIP_STAMP(5);
 
   // ---- epilogue: lane (u, g') holds n2 = 32 w + 8 g' + 2 e' + t in acc2[t][e']; lazy rescale, 16-byte stores, abs-sum
   pve = lane < a.PE ? pve : 0.0;
@@ -273,7 +265,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_lat(ZipLatArgs a) {
     for (int i = 0; i < 8; ++i) tot += red[i];
     a.partC[(size_t)r * a.partC_stride + mp * nub + ub] = tot;
   }
-  ZL_STAMP(6);
+  CTN_ZIP_STAMP(6);
 #undef ZL_EREQUEST
 }
 

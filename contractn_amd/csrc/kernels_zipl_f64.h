@@ -99,9 +99,7 @@ __global__ __launch_bounds__(512, 1) void k_zip_lat_f64(ZipLat64Args a) {
   const int i16 = lane & 15, h = lane >> 4;
   // every XCD a contiguous range of work items; items are ordered (m1 part, replica, u block), as in k_zip_lat (the
   // grid is a multiple of 8 here: S = 8)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int nub = a.U / 16, per_mp = a.R * nub;
   const int mp = pid / per_mp;
   const int rem = pid - mp * per_mp;

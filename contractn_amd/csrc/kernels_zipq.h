@@ -37,16 +37,12 @@ __global__ __launch_bounds__(256, 1) void k_zipq_f32(ZipArgs a) {
   const int lane = tid & 63;
   const int ub = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, h = lane >> 5;
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
-  const int pid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const int pid = zipq_pid(blockIdx.x, gridDim.x);
   const int per = a.U / ZU;                    // workgroups per replica
   const int r = pid / per;
   const int t_ = pid - r * per;
   const int u0 = t_ * ZU;
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 0] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(0);
   void* const* tp = a.ptrs + (size_t)r * a.n_tensors;
   const float* __restrict__ E = (const float*)tp[a.idE];
   const float* __restrict__ X = (const float*)tp[a.idX] + u0;
@@ -118,9 +114,7 @@ __global__ __launch_bounds__(256, 1) void k_zipq_f32(ZipArgs a) {
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0)
   __builtin_amdgcn_s_barrier();
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 1] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(1);
 
   // fragment double buffer: phase 1 f[10 b + mb] = E block mb, f[10 b + 8 + leg] = X; phase 2 f[10 b + nb] = Y block nb
   float f[20];
@@ -222,9 +216,7 @@ __global__ __launch_bounds__(256, 1) void k_zipq_f32(ZipArgs a) {
     for (int i = 0; i < 8; ++i) tot += red[i];
     a.partC[(size_t)r * a.partC_stride + t_] = tot;
   }
-#ifdef CTN_STAMPS
-  if (a.dbg && tid == 0) a.dbg[(size_t)pid * 8 + 3] = __builtin_amdgcn_s_memtime();
-#endif
+  CTN_ZIP_STAMP(3);
 }
 
 }  // namespace ctn

@@ -31,8 +31,9 @@ CTN_ZQI_FN int zipq_grid(int64_t items, int n_cu, int cap) {
   return items < (int64_t)c ? (items < 1 ? 1 : (int)items) : c;
 }
 
-// The XCD remap of the zipper kernels: consecutive block ids go round the 8 XCDs, so block `bid` becomes the workgroup
-// `pid` for which consecutive pids share an XCD (and its L2).  A permutation of 0 .. nwg - 1.
+// The XCD remap of every kernel that remaps its block id (the zipper kernels, the k_mfma_* tiles, k_cmfma_f32):
+// consecutive block ids go round the 8 XCDs, so block `bid` becomes the workgroup `pid` for which consecutive pids share
+// an XCD (and its L2).  A permutation of 0 .. nwg - 1.
 CTN_ZQI_FN int zipq_pid(int bid, int nwg) {
   const int xcd = bid & 7, slot = bid >> 3, q8 = nwg >> 3, r8 = nwg & 7;
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;

@@ -31,7 +31,7 @@ LOG_TOL = 1e-4           # the tolerance tests/test_gpu_parity.py uses for the l
 
 
 def expected_fused(net, form):
-    """The steps that must go out as k_zipm64_f32: the conditions at the head of kernels_zipm64.h on the pair's
+    """The steps that must go out as k_zipm64_f32: the conditions at the head of kernels_zipm.h on the pair's
     (K1, |u|, Q) - |u| a multiple of 64 and at most 512 workgroups per network, K1 a multiple of the tile depth 16 and two
     tiles at least; every leading dimension of these dense operands is |u| or 64, a multiple of 4.  Pair i of a net is the
     steps (2 i, 2 i + 1) of an isolated network and (2 i + 1, 2 i + 2) behind a chain's opening step.  A chain's first pair

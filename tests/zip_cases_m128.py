@@ -1,5 +1,5 @@
 """The open zipper networks of tests/zip_cases.py restated at |m1| = |n2| = 128, for the element-wise checks of the bond-128
-fused site pair (k_zip128_f32, contractn_amd/csrc/kernels_zip128.h).  Shared by tests/test_gpu_zip128_elements.py (GPU)
+fused site pair (k_zip128_f32, contractn_amd/csrc/kernels_zipm.h).  Shared by tests/test_gpu_zip128_elements.py (GPU)
 and tests/test_zip_cases_m128_host.py (no GPU).  Nothing here touches the engine: the reference is plain NumPy matmul.
 
 The same two families - "pair" (E a network input) and "chain" (<phi|psi> with phi's bonds all 128) - the same probe (a
