@@ -6,7 +6,7 @@
 // Every argument is one setting: the networks in flight (R, default 1), the chip's CUs (CU, default 256) and every
 // development switch a plain step's form depends on, by the name of its environment variable without the CTN_ prefix
 // (LAT, LAT_MAX_T, LAT_WG_X2, LAT64_MIN_K, SPLITK, SPLITK_MAX, SPLITK_FILL_LONG, H, HALVE_TILES, MFMA_G, MFMA_BK, G_BIG,
-// G_BIG_MIN_K, G_SPLITK, ARES, ARES_NTW) plus the switches of the fused forms that would take a step away from
+// G_BIG_MIN_K, G_SPLITK, ARES, ARES_NTW, DOT_TR) plus the switches of the fused forms that would take a step away from
 // step_form() (ZIP, ZIPQ, ZIPL, CPLX, SWEEP, CHAIN, GROUP) - filled into a DevSwitches directly, the environment is not
 // read.  For every plan, every setting, each of the chip sizes (the setting's CU, then 64 and 304) and every step one line
 // goes to stdout:
@@ -15,9 +15,14 @@
 //     Bt=<n> M=<n> N=<n> K=<n> swapped=<0|1> pblocks=<n> pcollapse=<0|1>                                   (the planner's Step)
 //     kind=<Kind by name> tm=<n> tn=<n> S=<n> T=<n> kchunk=<n> splits=<n> blocks=<n> partials=<n> collapse=<0|1> cblocks=<n> bk=<16|32|0>
 //     role=<P|A|Z|L|C> slots=<the region fused_forms() gives the step> ares=<ntw, 0 = not taken> avec=<0|1>
+//     H=<n> L=<n> Nv=<n> sAn=<n> sBn=<n> vecw=<1|2|4> kvec=<0|1> u=<1|4, 0 = no k_stream variant> u1=<1|4|0>   (the streaming decomposition)
+//     group=<length of the LeafGroup this step heads, else 0> dottr=<0|1> Ka=<n> Kb=<n> chain=<Plan::chain>
+//     divA=<0|1> divB=<0|1>                                        (the operand is a step's result: divided by its rescale on load)
 //
 // `splits` is the number of K slabs the launch really has (empty trailing ones dropped), `bk` the k-tile depth of the
-// register-staged fp32 kernel (0 for every other kind).  The form is evaluated with c_vec = Step::cvec: the last step's
+// register-staged fp32 kernel (0 for every other kind), `u` what stream_variant() gives a plain streaming step at the
+// plan's own vector width and this R, `u1` the same at vector width 1 (a final step whose caller's buffer is not 16-byte
+// aligned).  The form is evaluated with c_vec = Step::cvec: the last step's
 // also depends on the alignment of the caller's buffer, which the engine's own staging buffers satisfy.
 #include <cstdint>
 #include <cstdio>
@@ -65,6 +70,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     else if (key == "SWEEP") d.sweep = v;
     else if (key == "CHAIN") d.chain = v;
     else if (key == "GROUP") d.group = v;
+    else if (key == "DOT_TR") d.dot_tr = v;
     else return false;
     p = e + 1;
   }
@@ -86,14 +92,21 @@ static void print_steps(int plan, int set, const Plan& P, const Setting& st_, in
     const StepForm f = step_form(P, s, st_.R, cu, st_.sw, st.cvec);
     const bool slabs = f.S > 0 && f.kchunk > 0;
     const int bk = f.kind == Kind::Plain ? (f.tm == 64 ? 16 : mfma_bk((int)st.K, st_.sw)) : 0;
+    int u = 0, u1 = 0;
+    int64_t nq = 0;
+    if (f.kind == Kind::Stream) { stream_variant(st, st_.R, st.vecw, &u, &nq); stream_variant(st, st_.R, 1, &u1, &nq); }
+    const DotTr& dt = F.dot_tr[s];
     printf("plan %d set %d cu %d step %d last=%d kernel=%d modeA=%d modeB=%d tileM=%d tileN=%d cvec=%d Bt=%lld M=%lld N=%lld K=%lld "
            "swapped=%d pblocks=%d pcollapse=%d kind=%s tm=%d tn=%d S=%d T=%d kchunk=%d splits=%d blocks=%lld partials=%d collapse=%d "
-           "cblocks=%lld bk=%d role=%c slots=%d ares=%d avec=%d\n",
+           "cblocks=%lld bk=%d role=%c slots=%d ares=%d avec=%d H=%lld L=%lld Nv=%lld sAn=%lld sBn=%lld vecw=%d kvec=%d u=%d u1=%d group=%d "
+           "dottr=%d Ka=%d Kb=%d chain=%d divA=%d divB=%d\n",
            plan, set, cu, s, s + 1 == P.n_steps ? 1 : 0, st.kernel, st.modeA, st.modeB, st.tileM, st.tileN, st.cvec ? 1 : 0,
            (long long)st.Bt, (long long)st.M, (long long)st.N, (long long)st.K, st.swapped ? 1 : 0, st.blocks, st.collapse ? 1 : 0,
            kind_name(f.kind), f.tm, f.tn, f.S, f.T, f.kchunk, slabs ? form_splits(st, f) : 0, (long long)f.blocks, f.partials,
            f.collapse ? 1 : 0, (long long)f.collapse_blocks, bk, "PAZLC"[(int)F.role[s]], F.step_partials[s],
-           F.ares_ntw[s] & 0xffff, F.ares_ntw[s] >> 16);
+           F.ares_ntw[s] & 0xffff, F.ares_ntw[s] >> 16, (long long)st.H, (long long)st.L, (long long)st.Nv, (long long)st.sAn,
+           (long long)st.sBn, st.vecw, st.kvec ? 1 : 0, u, u1, F.groups[s].len, dt.on ? 1 : 0, dt.on ? dt.Ka : 0, dt.on ? dt.Kb : 0,
+           P.chain ? 1 : 0, st.lhs >= P.n_inputs ? 1 : 0, st.rhs >= P.n_inputs ? 1 : 0);
   }
 }
 

@@ -22,8 +22,9 @@ that does not get there; the expectations below were filled in from that driver,
 Not covered here (each has, or is to get, a file of its own):
   * the fused-product operand modes of the A side (modeA 3, 4, 5: launch_mfma_a cases 3 .. 5, engine.hip);
   * the epilogue-summed variants (EPW = true of k_mfma_f32, k_mfma_f32_h<.., .., 2 | 4>);
-  * the streaming, row-dot and dot kernels and k_stream_group;
   * the eager rescale mode (k_renorm), the backward tape and every fused form (zipper pairs, sweeps, complex pairs, chains).
+
+The streaming, row-dot and dot kernels and k_stream_group have their file: tests/stream_cases.py.
 
 k_mfma_f32_ares (`fused_forms()` puts it in front of step_form()) is here as kind "Ares": element by element as a final step,
 and with a consumer - a vector over n, an n x n probe being out of reach at its N - through its reported rescale factor.
