@@ -54,6 +54,7 @@
 #include "kernels_zipl_f64.h"
 #include "kernels_sweep.h"
 #include "kernels_sweep_f64.h"
+#include "kernels_sweep_small.h"
 #include "kernels_mfma_lat.h"
 #include "kernels_stream.h"
 #include "kernels_chain.h"
@@ -99,6 +100,7 @@ struct DeviceGuard {
 
 struct Exec {
   const Plan* plan = nullptr;
+  Plan own_plan;                       // `plan` points here when a small-bond sweep took a chain plan (fused_forms.h, unchained)
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -500,14 +502,58 @@ static int launch_sweep64(Exec* E, int s) {
 #undef CTN_SWEEP64_LAUNCH
   }
   const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
-  hipLaunchKernelGGL(k_sweep64_z, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
+  hipLaunchKernelGGL(k_sweep64_z<true>, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
                      (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
   Sweep64Finish f{};
   f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
   f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
   f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
   f.min_norm = P.stabilize ? P.min_norm : INFINITY;
-  hipLaunchKernelGGL(k_sweep64_finish, dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+  hipLaunchKernelGGL((k_sweep64_finish<double, true>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+  return CTN_OK;
+}
+
+// the last member of a small-bond sweep (CTN_SWEEP_SMALL=1): S sites of two member steps each (`two`) or of one
+template <bool TWO>
+static int launch_sweep_small(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const SweepDesc& sd = E->forms.sweep;
+  const int S = (int)sd.steps.size() / (TWO ? 2 : 1);
+  SweepSmallArgs w{};
+  w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
+  w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M; w.D = sd.D;
+  w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
+  producer_partials(E, sd.idIn, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
+  w.min_norm = P.min_norm;
+  w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
+  E->launched_form[s] = CTN_FORM_SWEEP_SMALL;
+  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns of C per wave, every site
+  {
+    const dim3 gs((unsigned)sd.J, (unsigned)R);
+    const int DB = (sd.D + 15) / 16;
+#define CTN_SWEEP_SMALL_LAUNCH(BB)                                                                          \
+    do {                                                                                                    \
+      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small_f32<BB, 4, TWO>), gs, dim3(64), 0, E->stream, w);   \
+      else hipLaunchKernelGGL((k_sweep_small_f32<BB, 2, TWO>), gs, dim3(64), 0, E->stream, w);              \
+    } while (0)
+    if (DB == 1) CTN_SWEEP_SMALL_LAUNCH(1);
+    else if (DB == 2) CTN_SWEEP_SMALL_LAUNCH(2);
+    else if (DB == 3) CTN_SWEEP_SMALL_LAUNCH(3);
+    else CTN_SWEEP_SMALL_LAUNCH(4);
+#undef CTN_SWEEP_SMALL_LAUNCH
+  }
+  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
+  const int T = (int)sd.steps.size();
+  hipLaunchKernelGGL(k_sweep64_z<TWO>, dim3((unsigned)T, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
+                     (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
+  Sweep64Finish f{};
+  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
+  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
+  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
+  hipLaunchKernelGGL((k_sweep64_finish<float, TWO>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
   return CTN_OK;
 }
 
@@ -561,7 +607,9 @@ static int launch_sweep_member(Exec* E, int s) {
   if (E->forms.sweep_role[s] == 1) return mark_absorbed(E, s);
   const StepTimer t(E, s);
   if (t.rc != CTN_OK) return t.rc;
-  const int rc = E->forms.sweep.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
+  const SweepDesc& sd = E->forms.sweep;
+  const int rc = sd.small ? (sd.two ? launch_sweep_small<true>(E, s) : launch_sweep_small<false>(E, s))
+                          : sd.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
   return rc != CTN_OK ? rc : t.end();
 }
 
@@ -1290,7 +1338,7 @@ int64_t ctn_plan_out_bytes(const ctn_plan* plan) {
 static int64_t exec_fixed_bytes(const Plan& P, int R) {
   const int nt = P.n_inputs + P.n_steps + 1;
   int64_t slots = 0;
-  for (const Step& st : P.steps) slots += std::max(st.partials, kWaveOutputs);   // (a launcher may retile: upper bound)
+  for (const Step& st : P.steps) slots += std::max(std::max(st.partials, st.partials_step), kWaveOutputs);   // (a launcher may retile: upper bound)
   return (int64_t)P.tables.size() * 4 + (int64_t)P.tables64.size() * 8 + (int64_t)R * nt * 8 + slots * R * 8 +
          (int64_t)R * std::max<int64_t>(P.max_collapse_blocks, 1) * 8 + (int64_t)R * 8 +
          (int64_t)R * P.n_steps * 8 + 256 + (int64_t)P.n_steps * 12;
@@ -1332,9 +1380,11 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   ctn_exec* x = new (std::nothrow) ctn_exec();
   if (!x) { g_err = "out of host memory"; return CTN_OOM; }
   Exec& E = x->e;
-  const Plan& P = plan->p;
-  E.plan = &P; E.device = device; E.R = replicas; E.n_cu = n_cu > 0 ? n_cu : 256;
   E.sw = read_dev_switches();
+  // (a small-bond sweep that is asked for takes a chain plan from the chain walker: the executor works on its own copy)
+  if (sweep_small_unchains(plan->p, E.sw)) E.own_plan = unchained(plan->p);
+  const Plan& P = E.own_plan.n_steps ? E.own_plan : plan->p;
+  E.plan = &P; E.device = device; E.R = replicas; E.n_cu = n_cu > 0 ? n_cu : 256;
   E.use_graph = E.sw.graph;
   E.launched_tile.assign(P.n_steps, 0);
   E.launched_form.assign(P.n_steps, 0);

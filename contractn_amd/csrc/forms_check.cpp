@@ -5,21 +5,24 @@
 //
 // Every argument is one setting: the networks in flight (R, default 1), the chip's CUs (CU, default 256) and development
 // switches by the names of their environment variables without the CTN_ prefix (ZIP, ZIPQ, ZIPL, ZIPL_MP, ZIPL_MAX_R, ZIPL64,
-// ZIP128, ZIPM64, ZIP512, CPLX, SWEEP, SWEEP64, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
-// environment is not read.  For every plan and every setting one line goes to stdout with everything an executor would
+// ZIP128, ZIPM64, ZIP512, CPLX, SWEEP, SWEEP64, SWEEP_SMALL, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
+// environment is not read.  ALIAS_LD=<n> is no switch but a change to the PLAN, for the one rule of the sweep matchers that
+// no planner-made layout reaches: the result of the run that sweep_small_match finds is moved onto the run's input in the
+// workspace, with rows n elements apart (a two-step run; n = the input's own row stride must stay taken, any other refused).
+// For every plan and every setting one line goes to stdout with everything an executor would
 // decide when it is created:
 //
 //   plan <i> set <j> rc=0 roles=<one letter per step: P plain, A absorbed, Z zip, L zip latency form, C complex>
 //     forms=[<step>:<ctn_step_form>/zu<zu>/zm<zm>,..] lat=[<step>:mp<mp>/prev<0|1>/next<0|1>/buf<0|1>,..] cplx=[<sp>+<step>,..]
 //     partials=<n per step,..> off=<per step,..> slots=<n> scratch=<n>
 //     bufs=slab:<n>,fold:<n>,zl:<n>,group:<n>,sweep:<a>/<s>/<z>/<l>/<e>,tabs:<n>
-//     sweep=[<member steps,..>]<f32|f64|-> ares=[<step>:<ntw>,..] dot=[<step>,..] groups=[<head>:<len>,..]
+//     sweep=[<member steps,..>]<f32|f64|small2|small1|-> ares=[<step>:<ntw>,..] dot=[<step>,..] groups=[<head>:<len>,..]
 //     side=[<tensor>:<buffer>,..]x<bytes>x<buffers> ok | <the invariant that failed>
 //
 // and these invariants are checked on each: a step's descriptor is on exactly under its role; an absorbed step is
 // directly followed by its pair's second member or named by a complex pair's `sp`; step_off is the running sum of
 // step_partials (a chain plan: one slot per step); no fused launch has more than kMaxPartials slots; two side buffers of
-// k_zipqp_f32 that are live at the same time never share an index.
+// k_zipqp_f32 that are live at the same time never share an index; no leaf group holds a sweep member or an absorbed step.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +35,7 @@
 
 using namespace ctn;
 
-struct Setting { int R = 1, cu = 256; DevSwitches sw; };
+struct Setting { int R = 1, cu = 256, alias_ld = 0; DevSwitches sw; };
 
 static bool parse_setting(const char* arg, Setting* out) {
   std::string s(arg);
@@ -44,6 +47,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     DevSwitches& d = out->sw;
     if (key == "R") out->R = v;
     else if (key == "CU") out->cu = v;
+    else if (key == "ALIAS_LD") out->alias_ld = v;
     else if (key == "ZIP") d.zip = v;
     else if (key == "ZIPQ") d.zipq = v;
     else if (key == "ZIPL") d.zipl = v;
@@ -56,6 +60,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     else if (key == "CPLX") d.cplx = v;
     else if (key == "SWEEP") d.sweep = v;
     else if (key == "SWEEP64") d.sweep64 = v;
+    else if (key == "SWEEP_SMALL") d.sweep_small = v;
     else if (key == "GROUP") d.group = v;
     else if (key == "ARES") d.ares = v;
     else if (key == "ARES_NTW") d.ares_ntw = v;
@@ -98,6 +103,10 @@ static std::string invariants(const Plan& P, const FusedForms& F) {
     for (int s = 0; s < n; ++s)
       if (F.role[s] != Role::Plain || F.sweep_role[s] || F.ares_ntw[s] || F.dot_tr[s].on || F.groups[s].len)
         return "a chain plan with a fused form";
+  for (int s = 0; s < n; ++s)
+    for (int i = 0; i < F.groups[s].len; ++i)
+      if (s + i >= n || F.sweep_role[s + i] || F.role[s + i] == Role::Absorbed)
+        return "step " + std::to_string(s + i) + ": in a leaf group and never launched on its own";
   // side buffers: tensor id (the result of pair s, consumed by step c) holds its buffer over steps [s - 1, c]
   struct Live { int k, from, to; };
   std::vector<Live> live;
@@ -142,7 +151,7 @@ static void print_line(int plan, int set, const Plan& P, const FusedForms& F) {
          "side=[%s]x%lldx%d %s\n",
          plan, set, roles.c_str(), forms.c_str(), lat.c_str(), cplx.c_str(), partials.c_str(), offs.c_str(), (long long)F.part_slots,
          (long long)F.scratch_need, F.slab_elems, F.fold_elems, (long long)F.zl_slab_elems, F.group_args, F.sweep_a, F.sweep_s,
-         F.sweep_z, F.sweep_l, F.sweep_e, F.cplx_tabs.size(), sweep.c_str(), !F.sweep.on ? "-" : F.sweep.f64 ? "f64" : "f32",
+         F.sweep_z, F.sweep_l, F.sweep_e, F.cplx_tabs.size(), sweep.c_str(), !F.sweep.on ? "-" : F.sweep.small ? (F.sweep.two ? "small2" : "small1") : F.sweep.f64 ? "f64" : "f32",
          ares.c_str(), dot.c_str(), groups.c_str(), side.c_str(), (long long)F.zqp_side_bytes, F.zqp_side_bufs,
          invariants(P, F).c_str());
 }
@@ -187,9 +196,17 @@ int main(int argc, char** argv) {
     ++n_plans;
     if (rc != CTN_OK) { printf("plan %d rc=%d %s\n", n_plans, rc, err.c_str()); ++n_fail; continue; }
     for (size_t j = 0; j < sets.size(); ++j) {
-      const FusedForms F = fused_forms(P, sets[j].R, sets[j].cu, sets[j].sw);
-      if (invariants(P, F) != "ok") ++n_fail;
-      print_line(n_plans, (int)j, P, F);
+      // (a small-bond sweep that is asked for takes a chain plan from the chain walker: the executor's own first decision)
+      Plan Q = sweep_small_unchains(P, sets[j].sw) ? unchained(P) : P;
+      SweepDesc sd;
+      if (sets[j].alias_ld > 0 && sweep_small_match(Q, &sd) && sd.two && sd.idIn >= Q.n_inputs) {
+        Tensor& out = Q.tensors[Q.steps[sd.steps.back()].out];
+        out.ws_offset = Q.tensors[sd.idIn].ws_offset;
+        for (int64_t& st : out.strides) if (st != 1) st = sets[j].alias_ld;
+      }
+      const FusedForms F = fused_forms(Q, sets[j].R, sets[j].cu, sets[j].sw);
+      if (invariants(Q, F) != "ok") ++n_fail;
+      print_line(n_plans, (int)j, Q, F);
     }
   }
   return n_fail ? 1 : 0;

@@ -58,6 +58,9 @@ struct SweepDesc {
   bool f64 = false;
   int idIn = -1;
   std::vector<int32_t> ids;
+  // small bonds (kernels_sweep_small.h, float32): `two` - the members are the 2 S steps of S two-step sites, as in
+  // float64; else the S epilogue-summed steps.  ids and idIn are filled in both shapes.
+  bool small = false, two = false;
 };
 // A full dot of a tensor with a transposed one (k_dot_tr), found on the plan's tables
 struct DotTr { bool on = false; int Ka = 0, Kb = 0, x_is_a = 1; int64_t ldY = 0; };
@@ -159,13 +162,16 @@ static constexpr bool kCplxDefault = false;
 
 // Is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
 // offset tables: E row-major [b][l], W[l][p][r] with r unit-stride, x[b][p] with p unit-stride, result rows [b][r].
+// `small`: as one site of k_sweep_small_f32 instead - any bond 8 ... 64 that is a multiple of 4, x rows of any stride >= |p|.
 struct SweepShape { int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
-inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh) {
+inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh, bool small = false) {
   const Step& st = P.steps[s];
   const int D = (int)st.K, Pd = st.epw;
-  if (P.dtype != CTN_F32 || st.kernel != CTN_KERNEL_MFMA_F32 || (Pd != 2 && Pd != 4) || st.Bt != 1 ||
-      (st.K != 64 && st.K != 128 && st.K != 256 && st.K != 512) || st.N != (int64_t)D * Pd || s + 1 >= P.n_steps)
+  const bool bond_ok = small ? (st.K >= 8 && st.K <= 64 && st.K % 4 == 0) : (st.K == 64 || st.K == 128 || st.K == 256 || st.K == 512);
+  if (P.dtype != CTN_F32 || st.kernel != CTN_KERNEL_MFMA_F32 || (Pd != 2 && Pd != 4) || st.Bt != 1 || !bond_ok ||
+      st.N != (int64_t)D * Pd || s + 1 >= P.n_steps)
     return false;
+  if (small && st.M >= ((int64_t)1 << 31) - kFormSWR) return false;
   // (st.collapse - the step's OWN launch would have more workgroups than partial slots and leave one collapsed slot - is
   // no obstacle: a member is never launched, and k_sweep_finish fills however many slots the step has, slot 0 first)
   if (st.rhs < 0 || st.rhs >= P.n_inputs || st.lhs2 < 0 || st.lhs2 >= P.n_inputs) return false;   // W, x: network inputs
@@ -188,20 +194,20 @@ inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh) {
     if (off < 0 || pp >= Pd || rr >= D || onC[n] != rr || seen[(size_t)(pp * D + rr)]) return false;
     seen[(size_t)(pp * D + rr)] = 1;
   }
-  if (ldA < D || ldC < D || ldA % 4 || ldC % 4 || ldX % Pd || ldX < Pd || ldWl % 4 || ldWp % 4 || ldWl < D) return false;
+  if (ldA < D || ldC < D || ldA % 4 || ldC % 4 || (!small && ldX % Pd) || ldX < Pd || ldWl % 4 || ldWp % 4 || ldWl < D) return false;
   if (((D + 12) * ldWl + 3 * ldWp + D) * 4 >= ((int64_t)1 << 31)) return false;   // a lane's offsets into a core: 32 bits
   sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = D; sh->Pd = Pd;
   return true;
 }
 
-// The longest run of such steps, each taking the result of the one before as its E.
-inline bool sweep_match(const Plan& P, SweepDesc* d) {
+// The longest run of such steps, each taking the result of the one before as its E.  (`small`: see sweep_step_shape.)
+inline bool sweep_match(const Plan& P, SweepDesc* d, bool small = false) {
   std::vector<int> best;
   SweepShape best_first, best_last;
   std::vector<char> used((size_t)P.n_steps, 0);
   for (int s0 = 0; s0 < P.n_steps; ++s0) {
     SweepShape first, cur, last;
-    if (used[s0] || !sweep_step_shape(P, s0, &first)) continue;
+    if (used[s0] || !sweep_step_shape(P, s0, &first, small)) continue;
     std::vector<int> run{s0};
     last = first;
     for (int s = s0 + 1; s < P.n_steps; ++s) {
@@ -214,7 +220,7 @@ inline bool sweep_match(const Plan& P, SweepDesc* d) {
           P.steps[s].lhs2 != P.steps[run.back()].out)
         break;
       // the consumer of the run's last result: a member if it has the same shape and takes it as its E
-      if (P.steps[s].lhs == P.steps[run.back()].out && sweep_step_shape(P, s, &cur) && cur.M == first.M && cur.D == first.D &&
+      if (P.steps[s].lhs == P.steps[run.back()].out && sweep_step_shape(P, s, &cur, small) && cur.M == first.M && cur.D == first.D &&
           cur.Pd == first.Pd && cur.ldWl == first.ldWl && cur.ldWp == first.ldWp && cur.ldX == first.ldX && cur.ldA == last.ldC) {
         run.push_back(s);
         last = cur;
@@ -240,7 +246,11 @@ inline bool sweep_match(const Plan& P, SweepDesc* d) {
       if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
     }
   }
-  d->on = true; d->steps = best;
+  d->on = true; d->steps = best; d->small = small;
+  if (small) {
+    d->idIn = P.steps[best.front()].lhs;
+    for (int s : best) { d->ids.push_back(P.steps[s].rhs); d->ids.push_back(P.steps[s].lhs2); }
+  }
   d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
   d->J = (int)((best_first.M + kFormSWR - 1) / kFormSWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
   return true;
@@ -254,14 +264,20 @@ static constexpr bool kSweepF64Default = false;
 // the pair as one site?  Matched on the tensors' labels, dims and strides: E and E' row-major [b][.], r unit-stride in W,
 // p unit-stride in x, every stride even (16-byte accesses).  The layout the planner gave C does not matter: C is never
 // written.
+// `small`: the same pair in float32 at a small bond, as one site of k_sweep_small_f32 (kernels_sweep_small.h) - the planner
+// keeps a float32 site as two steps too while its epilogue-summed step would be small (plan.cpp: M >= 64, N >= 32, K >= 8,
+// M N >= 65536): any bond 8 ... 64 that is a multiple of 4, every stride of E, E' and W a multiple of 4 (16-byte accesses
+// of the state's rows), x rows of any stride >= |p|.
 struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
-inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh) {
-  if (P.dtype != CTN_F64 || sb + 1 >= P.n_steps) return false;              // a step must follow the last member
+inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, bool small = false) {
+  if (P.dtype != (small ? CTN_F32 : CTN_F64) || sb + 1 >= P.n_steps) return false;   // a step must follow the last member
   const Step& a = P.steps[sa];
   const Step& b = P.steps[sb];
-  if (a.kernel != CTN_KERNEL_MFMA_F64 || b.kernel != CTN_KERNEL_ELEMENT || a.rhs < 0 || b.rhs < 0 || a.lhs2 >= 0 || b.lhs2 >= 0 ||
-      a.epw || b.epw)
+  // (small: whichever kernels the planner gave the two steps - at a few rows the GEMM is a streaming step itself; what the
+  // steps compute is read off the labels below, and neither is launched)
+  if (small ? (a.kernel == CTN_KERNEL_FUSED || b.kernel == CTN_KERNEL_FUSED) : (a.kernel != CTN_KERNEL_MFMA_F64 || b.kernel != CTN_KERNEL_ELEMENT))
     return false;
+  if (a.rhs < 0 || b.rhs < 0 || a.lhs2 >= 0 || b.lhs2 >= 0 || a.epw || b.epw) return false;
   auto axis = [](const Tensor& t, int32_t lab) {
     int found = -1;
     for (size_t i = 0; i < t.labels.size(); ++i)
@@ -283,12 +299,14 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh) {
   if (lr == ll || lr == lp || lr == lb) return false;
   if (axis(tC, lb) < 0 || axis(tC, lp) < 0 || axis(tC, lr) < 0 || axis(tO, lb) < 0 || axis(tO, lr) < 0) return false;
   const int64_t D = tE.dims[el], Pd = tW.dims[axis(tW, lp)], M = tE.dims[1 - el];
-  if ((D != 64 && D != 128 && D != 256 && D != 512) || (Pd != 2 && Pd != 4) || tW.dims[axis(tW, lr)] != D || M >= ((int64_t)1 << 31) - kFormSWR)
+  const bool bond_ok = small ? (D >= 8 && D <= 64 && D % 4 == 0) : (D == 64 || D == 128 || D == 256 || D == 512);
+  if (!bond_ok || (Pd != 2 && Pd != 4) || tW.dims[axis(tW, lr)] != D || M >= ((int64_t)1 << 31) - kFormSWR)
     return false;
   if (tE.strides[el] != 1 || tW.strides[axis(tW, lr)] != 1 || tX.strides[axis(tX, lp)] != 1 || tO.strides[axis(tO, lr)] != 1) return false;
   const int64_t ldA = tE.strides[1 - el], ldC = tO.strides[axis(tO, lb)], ldX = tX.strides[axis(tX, lb)];
   const int64_t ldWl = tW.strides[axis(tW, ll)], ldWp = tW.strides[axis(tW, lp)];
-  if (ldA < D || ldC < D || ldX < Pd || ldWl <= 0 || ldWp <= 0 || ((ldA | ldC | ldX | ldWl | ldWp) & 1)) return false;
+  if (ldA < D || ldC < D || ldX < Pd || ldWl <= 0 || ldWp <= 0) return false;
+  if (small ? ((ldA | ldC | ldWl | ldWp) & 3) != 0 : ((ldA | ldC | ldX | ldWl | ldWp) & 1) != 0) return false;
   if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;   // a lane's offsets into a core: 32 bits, in bytes
   sh->idE = idE; sh->idW = idW; sh->idX = idX; sh->idOut = b.out;
   sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = (int)D; sh->Pd = (int)Pd;
@@ -298,7 +316,7 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh) {
 // The longest run of such pairs, each taking the result of the one before as its E.  The two safety rules are those of
 // sweep_match: nothing that is launched may lie between two members, and the run's result may overlap its input only as
 // the same region with the same row stride.
-inline bool sweep64_match(const Plan& P, SweepDesc* d) {
+inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
   auto next_launched = [&](int s) { do ++s; while (s < P.n_steps && P.steps[s].kernel == CTN_KERNEL_FUSED); return s; };
   std::vector<int> best;
   std::vector<int32_t> best_ids;
@@ -307,14 +325,14 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d) {
   for (int s0 = 0; s0 < P.n_steps; ++s0) {
     Sweep64Site first, cur, last;
     int sb = next_launched(s0);
-    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first)) continue;
+    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first, small)) continue;
     std::vector<int> run{s0, sb};
     std::vector<int32_t> ids{first.idW, first.idX};
     last = first;
     for (;;) {
       const int na = next_launched(run.back());
       const int nb = na < P.n_steps ? next_launched(na) : na;
-      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
+      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur, small) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
           cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC)
         break;
       run.push_back(na); run.push_back(nb);
@@ -336,10 +354,49 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d) {
       if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
     }
   }
-  d->on = true; d->f64 = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
+  d->on = true; d->f64 = !small; d->small = small; d->two = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
   d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
   d->J = (int)((best_first.M + kFormSWR - 1) / kFormSWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
   return true;
+}
+
+// Is k_sweep_small_f32 taken without CTN_SWEEP_SMALL=1 wherever sweep_small_match takes a run?  Decided by measurement
+// (DESIGN sections 10 and 11): tools/sweep_small_timing.py has to show the one launch ahead of the per-site launches by
+// more than the larger spread at every one of its shapes, and the small-bond GPU suite has to be green with CTN_SWEEP_SMALL=1.
+static constexpr bool kSweepSmallDefault = false;
+
+// A float32 batched MPS of bond 8 ... 64 (kernels_sweep_small.h) in either shape the planner gives its sites: the longest run
+// of two-step sites (sweep64_match on the float32 plan) or of epilogue-summed steps (sweep_match at the small bonds),
+// whichever walks more sites.  Both matchers keep their two safety rules: nothing launched between members, and the
+// run's result overlaps its input only as the same region with the same row stride.  At most kFormSweepMaxSites sites.
+inline bool sweep_small_match(const Plan& P, SweepDesc* d) {
+  if (P.dtype != CTN_F32) return false;
+  SweepDesc two, one;
+  const bool m2 = sweep64_match(P, &two, true), m1 = sweep_match(P, &one, true);
+  if (!m1 && !m2) return false;
+  *d = (m2 && (!m1 || two.steps.size() / 2 >= one.steps.size())) ? two : one;
+  return (int)(d->two ? d->steps.size() / 2 : d->steps.size()) <= kFormSweepMaxSites;
+}
+
+// Is the small-bond sweep asked for on this plan?  Only on request (CTN_SWEEP_SMALL=1) while kSweepSmallDefault is off, and
+// never against CTN_SWEEP=0.
+inline bool sweep_small_asked(const Plan& P, const DevSwitches& sw) {
+  return sw.sweep != 0 && P.stabilize && (sw.sweep_small == 1 || (kSweepSmallDefault && sw.sweep_small != 0));
+}
+
+// A chain plan (Plan::chain: every step small) is walked whole by the chain walker and has no fused form - most
+// small-bond classifiers with a batch of a few dozen are such plans.  A small-bond sweep that is asked for and matches
+// takes the plan from the walker: the executor (and forms_check) then works on a copy whose steps are launches of their
+// own again, with the slot counts and collapse flags the planner gave them before it marked the plan.
+inline bool sweep_small_unchains(const Plan& P, const DevSwitches& sw) {
+  SweepDesc d;
+  return P.chain && sweep_small_asked(P, sw) && sweep_small_match(P, &d);
+}
+inline Plan unchained(const Plan& P) {
+  Plan Q = P;
+  Q.chain = false;
+  for (Step& st : Q.steps) { st.partials = st.partials_step; st.collapse = st.collapse_step; }
+  return Q;
 }
 
 // Is this split dot step the sum over k = (a, b) of X[a Kb + b] Y[b ldY + a] - one operand contiguous in k, the other
@@ -671,7 +728,7 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.ares_ntw[s] = ares_match(P, s, R, n_cu, sw);
       if (F.ares_ntw[s] && ares_avec(P, s)) F.ares_ntw[s] |= 1 << 16;
     }
-  // a sweep: at least half a chip of row blocks, or CTN_SWEEP=1
+  // a sweep: at least half a chip of row blocks, or CTN_SWEEP=1; at the small bonds only on request (CTN_SWEEP_SMALL=1)
   if (sw.sweep != 0 && P.stabilize) {
     SweepDesc sd;
     // (bonds up to 128: the per-site launches are a few microseconds of latency each whatever the batch - always)
@@ -688,6 +745,13 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.sweep_ids = sd.ids;
       F.sweep_a = 2 * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * T;
       F.sweep = sd;
+    } else if (SweepDesc ss; sweep_small_asked(P, sw) && sweep_small_match(P, &ss)) {
+      // small bonds (k_sweep_small_f32), only where neither form above took the plan: a record per (site, row block) and
+      // member entry - two per site of the two-step shape, one of the epilogue-summed shape
+      const size_t S = ss.two ? ss.steps.size() / 2 : ss.steps.size(), nrec = (size_t)R * S * ss.J;
+      F.sweep_ids = ss.ids;
+      F.sweep_a = (ss.two ? 2 : 1) * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * ss.steps.size();
+      F.sweep = ss;
     }
     for (int s : F.sweep.steps) {
       F.sweep_role[s] = s == F.sweep.steps.back() ? 2 : 1;
@@ -700,7 +764,9 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       const Step& st = P.steps[s];
       if (st.kernel != CTN_KERNEL_ELEMENT || st.kvec || st.collapse || s + 1 >= n || st.rhs < 0 ||
           st.lhs >= P.n_inputs || st.rhs >= P.n_inputs || st.lhs2 >= 0 || stream_splits(st, R, n_cu) ||
-          F.role[s] == Role::Absorbed)      // (a streaming step is absorbed as the S step of a complex pair: never launched)
+          F.role[s] == Role::Absorbed ||    // (a streaming step is absorbed as the S step of a complex pair: never launched)
+          F.sweep_role[s])                  // (... or is a member of a sweep: at a few rows the E . W_1 step of a small-bond
+                                            // two-step site is a streaming step on two network inputs)
         return false;
       int64_t nq;
       *vw = st.vecw;

@@ -254,12 +254,16 @@ __global__ __launch_bounds__(Sweep64Shape<D>::NT, 1) void k_sweep_f64(Sweep64Arg
 // terms are scaled by ldexp to the largest exponent among them (exact), summed in a fixed order, and the mean m 2^x
 // (1 <= m < 2) gives Z = log(m) + x ln 2: one log, one product, one sum - and exactly 0 for a mean of exactly 1.
 // -inf: an all-zero tensor; NaN: a non-finite record.  grid (2 S, R), 256 threads.
+// <TWO>: true - the float64 sweep and the two-step sites of k_sweep_small_f32, as described; false (the epilogue-summed sites
+// of k_sweep_small_f32, kernels_sweep_small.h) - ONE entry per site, E'_s: grid (S, R), rec_a [R][S][J], Z [R][S].
+template <bool TWO>
 __global__ __launch_bounds__(256) void k_sweep64_z(const double* __restrict__ rec_a, const int32_t* __restrict__ rec_e, int S, int J,
                                                    double numelC, double numelE, double* __restrict__ Z) {
   __shared__ double red[4];
   __shared__ int redi[4];
-  const int t = blockIdx.x, s = t >> 1, r = blockIdx.y;
-  const double* pa = rec_a + ((size_t)r * 2 * S + t) * J;
+  constexpr int NE = TWO ? 2 : 1;              // entries per site
+  const int t = blockIdx.x, s = TWO ? t >> 1 : t, r = blockIdx.y;
+  const double* pa = rec_a + ((size_t)r * NE * S + t) * J;
   const int32_t* pe = rec_e + (size_t)r * S * J;
   constexpr int kNone = INT32_MIN, kBad = INT32_MAX;
   int mx = kNone;
@@ -278,7 +282,7 @@ __global__ __launch_bounds__(256) void k_sweep64_z(const double* __restrict__ re
   __syncthreads();
   mx = max(max(redi[0], redi[1]), max(redi[2], redi[3]));
   if (mx == kNone || mx == kBad) {            // (uniform over the workgroup)
-    if (threadIdx.x == 0) Z[(size_t)r * 2 * S + t] = mx == kNone ? -INFINITY : NAN;
+    if (threadIdx.x == 0) Z[(size_t)r * NE * S + t] = mx == kNone ? -INFINITY : NAN;
     return;
   }
   double sum = 0.0;
@@ -292,31 +296,34 @@ __global__ __launch_bounds__(256) void k_sweep64_z(const double* __restrict__ re
   }
   const double tot = block_sum(sum, red);
   if (threadIdx.x == 0) {
-    const double ratio = tot / ((t & 1) ? numelE : numelC);
+    const double ratio = tot / ((!TWO || (t & 1)) ? numelE : numelC);
     const int x0 = ilogb(ratio);
-    Z[(size_t)r * 2 * S + t] = log(ldexp(ratio, -x0)) + (double)(x0 + mx) * 0.6931471805599453094;
+    Z[(size_t)r * NE * S + t] = log(ldexp(ratio, -x0)) + (double)(x0 + mx) * 0.6931471805599453094;
   }
 }
 
 // k_sweep64_finish: the reference's rescale factors of the 2 S member steps from the Z_t, and the last site's rows at the
-// common scale.  grid (J, R), 256 threads.
+// common scale.  grid (J, R), 256 threads.  <T, TWO>: the element type of the rows (double; float: k_sweep_small_f32, whose
+// rows are D % 4 == 0 floats - the same 16-byte pieces) and, as in k_sweep64_z, whether a site has two entries or one.
 struct Sweep64Finish {
   void* const* ptrs;
   int32_t n_tensors, idOut, S, J, R, D, M;   // D: bond dimension; M: rows (the last block may hold fewer than 16)
   int64_t ldOut;
-  const double* Z;           // [R][2 S]
+  const double* Z;           // [R][2 S] ([R][S]: one entry per site)
   const int32_t* rec_e;      // [R][S][J]
-  const int64_t* part_off;   // [2 S]: the step's region in the partials buffer starts at part_off[t] * R doubles
-  const int32_t* part_slots; // [2 S]: slots per replica of that region
+  const int64_t* part_off;   // [2 S] ([S]): the step's region in the partials buffer starts at part_off[t] * R doubles
+  const int32_t* part_slots; // [2 S] ([S]): slots per replica of that region
   double* partials;
   double numelC, numelE, min_norm;
 };
 
+template <typename T_, bool TWO>
 __global__ __launch_bounds__(256) void k_sweep64_finish(Sweep64Finish f) {
-  __shared__ double norm[2 * kSweepMaxSites];
+  static_assert(sizeof(T_) == 8 || sizeof(T_) == 4, "double or float");
+  __shared__ double norm[(TWO ? 2 : 1) * kSweepMaxSites];
   __shared__ double common;
   __shared__ int shift;
-  const int j = blockIdx.x, r = blockIdx.y, T = 2 * f.S;
+  const int j = blockIdx.x, r = blockIdx.y, T = TWO ? 2 * f.S : f.S;
   const double* Z = f.Z + (size_t)r * T;
   if (threadIdx.x == 0) {
     // the reference's recurrence (einsum.py:97-106 over the chain's steps): norm_t = numel_t exp(Z_t) / R_{t-1}; rescaled
@@ -324,7 +331,7 @@ __global__ __launch_bounds__(256) void k_sweep64_finish(Sweep64Finish f) {
     double logR = 0.0, logR_before_last = 0.0;
     for (int t = 0; t < T; ++t) {
       const double z = Z[t];
-      const double nv = z == -INFINITY ? 0.0 : z != z ? INFINITY : ((t & 1) ? f.numelE : f.numelC) * exp(z - logR);
+      const double nv = z == -INFINITY ? 0.0 : z != z ? INFINITY : ((!TWO || (t & 1)) ? f.numelE : f.numelC) * exp(z - logR);
       if (t + 1 == T) logR_before_last = logR;
       norm[t] = nv;
       if (nv > f.min_norm && z == z) logR = z;
@@ -348,14 +355,29 @@ __global__ __launch_bounds__(256) void k_sweep64_finish(Sweep64Finish f) {
   }
   const double fac = common;
   const int sh = shift;
-  double* out = (double*)f.ptrs[(size_t)r * f.n_tensors + f.idOut] + (int64_t)(SWR * j) * f.ldOut;
-  const int rows = min(SWR, f.M - SWR * j), q2 = f.D / 2;
-  for (int i = threadIdx.x; i < rows * q2; i += 256) {
-    const int row = i / q2, c2 = i - row * q2;
-    double2* p = reinterpret_cast<double2*>(out + (int64_t)row * f.ldOut) + c2;
-    double2 v = *p;
-    v.x = ldexp(v.x * fac, sh); v.y = ldexp(v.y * fac, sh);
-    *p = v;
+  const int rows = min(SWR, f.M - SWR * j);
+  if constexpr (sizeof(T_) == 8) {
+    double* out = (double*)f.ptrs[(size_t)r * f.n_tensors + f.idOut] + (int64_t)(SWR * j) * f.ldOut;
+    const int q2 = f.D / 2;
+    for (int i = threadIdx.x; i < rows * q2; i += 256) {
+      const int row = i / q2, c2 = i - row * q2;
+      double2* p = reinterpret_cast<double2*>(out + (int64_t)row * f.ldOut) + c2;
+      double2 v = *p;
+      v.x = ldexp(v.x * fac, sh); v.y = ldexp(v.y * fac, sh);
+      *p = v;
+    }
+  } else {
+    // float rows: the common factor rounded to float ONCE (the same number in every block), then as above
+    const float ff = (float)fac;
+    float* out = (float*)f.ptrs[(size_t)r * f.n_tensors + f.idOut] + (int64_t)(SWR * j) * f.ldOut;
+    const int q4 = f.D / 4;
+    for (int i = threadIdx.x; i < rows * q4; i += 256) {
+      const int row = i / q4, c4 = i - row * q4;
+      float4* p = reinterpret_cast<float4*>(out + (int64_t)row * f.ldOut) + c4;
+      float4 v = *p;
+      v.x = ldexpf(v.x * ff, sh); v.y = ldexpf(v.y * ff, sh); v.z = ldexpf(v.z * ff, sh); v.w = ldexpf(v.w * ff, sh);
+      *p = v;
+    }
   }
 }
 

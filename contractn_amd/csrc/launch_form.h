@@ -31,6 +31,8 @@ struct DevSwitches {
   int sweep = -1;        // CTN_SWEEP: 0 never walk a chain of epilogue-summed steps in one launch (k_sweep_f32), 1 whenever one matches (tests)
   int sweep64 = 1;       // CTN_SWEEP64=0: never the float64 sweep (k_sweep_f64), which CTN_SWEEP=1 takes on a float64 plan whose
                          // per-site step pairs (a GEMM and the streaming sum over p) match
+  int sweep_small = -1;  // CTN_SWEEP_SMALL: 1 a float32 batched MPS of bond 8 ... 64 is walked in one launch (k_sweep_small_f32) wherever
+                         // sweep_small_match takes it, k_sweep_f32 does not and CTN_SWEEP is not 0; 0 or unset: never (kSweepSmallDefault)
   int dot_tr = 1;        // CTN_DOT_TR=0: full dots against a transposed tensor stay on k_dot_split's 4-byte gathers
   int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches
                          // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
@@ -99,6 +101,7 @@ inline DevSwitches read_dev_switches() {
   d.dot_tr = num("CTN_DOT_TR", 1);
   d.sweep = num("CTN_SWEEP", -1);
   d.sweep64 = num("CTN_SWEEP64", 1);
+  d.sweep_small = num("CTN_SWEEP_SMALL", -1);
   d.lat64_min_k = num("CTN_LAT64_MIN_K", 512);
   d.splitk_fill_long = num("CTN_SPLITK_FILL_LONG", 2);
   d.lat_max_t = num("CTN_LAT_MAX_T", 64);

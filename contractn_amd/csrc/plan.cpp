@@ -877,6 +877,7 @@ int build_plan(const ctn_plan_desc& d, Plan& P, std::string& err) {
   P.chain = d.n_steps >= 4 && d.n_steps <= kChainMaxSteps;
   for (const Step& st : P.steps)
     if (!st.chain_ok) P.chain = false;
+  for (Step& st : P.steps) { st.partials_step = st.partials; st.collapse_step = st.collapse; }
   if (P.chain)
     for (Step& st : P.steps) { st.partials = 1; st.collapse = false; }
   P.ws_bytes_per_replica = arena.top;

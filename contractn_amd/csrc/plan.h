@@ -77,6 +77,8 @@ struct Step {
   int blocks = 1;      // workgroups per replica
   int partials = 1;    // partial abs-sums per replica after the optional collapse pass
   bool collapse = false;
+  int partials_step = 1;        // what `partials` and `collapse` were before a chain plan set them to (1, false): the step
+  bool collapse_step = false;   // as a launch of its own (fused_forms.h, unchained)
   double flops = 0;
   TableRefs t;
 };

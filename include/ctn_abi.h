@@ -315,7 +315,9 @@ typedef enum {
   CTN_FORM_ZIP_F64 = 6, /* k_zip_f64 */
   CTN_FORM_ZIPQP = 7,   /* k_zipqp_f32: k_zipq_f32 with a workgroup that walks several work items of the launch */
   CTN_FORM_ZIPL_F64 = 8, /* k_zip_lat_f64: the float64 latency form, tile (32, 256) (the fp32 latency form k_zip_lat reports NONE) */
-  CTN_FORM_ZIP512 = 9   /* k_zip512_f32: the bond-512 pair on 16 x 16 x 4 MFMAs, 64 values of u per workgroup, tile (512, 512) */
+  CTN_FORM_ZIP512 = 9,  /* k_zip512_f32: the bond-512 pair on 16 x 16 x 4 MFMAs, 64 values of u per workgroup, tile (512, 512) */
+  CTN_FORM_SWEEP_SMALL = 10 /* k_sweep_small_f32: a batched MPS of bond 8 ... 64 in one launch, at its last member step, tile (16, D P) -
+                               the one form here that is no zipper pair (k_sweep_f32 and k_sweep_f64 report NONE) */
 } ctn_step_form;
 int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form);
 
