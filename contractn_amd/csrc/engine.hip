@@ -55,6 +55,7 @@
 #include "kernels_sweep.h"
 #include "kernels_sweep_f64.h"
 #include "kernels_sweep_small.h"
+#include "kernels_sweep_small_f64.h"
 #include "kernels_mfma_lat.h"
 #include "kernels_stream.h"
 #include "kernels_chain.h"
@@ -557,6 +558,49 @@ static int launch_sweep_small(Exec* E, int s) {
   return CTN_OK;
 }
 
+// the last member of a float64 small-bond sweep (CTN_SWEEP_SMALL64=1): S sites of two member steps each; the bookkeeping
+// launches are launch_sweep64's
+static int launch_sweep_small_f64(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const SweepDesc& sd = E->forms.sweep;
+  const int S = (int)sd.steps.size() / 2;
+  SweepSmallArgs w{};
+  w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
+  w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M; w.D = sd.D;
+  w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
+  producer_partials(E, sd.idIn, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
+  w.min_norm = P.min_norm;
+  w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
+  E->launched_form[s] = CTN_FORM_SWEEP_SMALL_F64;
+  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns of C per wave, every site
+  {
+    const dim3 gs((unsigned)sd.J, (unsigned)R);
+    const int DB = (sd.D + 15) / 16;
+#define CTN_SWEEP_SMALL64_LAUNCH(BB)                                                                    \
+    do {                                                                                                \
+      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small_f64<BB, 4>), gs, dim3(64), 0, E->stream, w);    \
+      else hipLaunchKernelGGL((k_sweep_small_f64<BB, 2>), gs, dim3(64), 0, E->stream, w);               \
+    } while (0)
+    if (DB == 1) CTN_SWEEP_SMALL64_LAUNCH(1);
+    else if (DB == 2) CTN_SWEEP_SMALL64_LAUNCH(2);
+    else if (DB == 3) CTN_SWEEP_SMALL64_LAUNCH(3);
+    else CTN_SWEEP_SMALL64_LAUNCH(4);
+#undef CTN_SWEEP_SMALL64_LAUNCH
+  }
+  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
+  hipLaunchKernelGGL(k_sweep64_z<true>, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
+                     (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
+  Sweep64Finish f{};
+  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
+  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
+  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
+  hipLaunchKernelGGL((k_sweep64_finish<double, true>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+  return CTN_OK;
+}
+
 // the last member of a sweep: the whole chain, then its scale bookkeeping
 static int launch_sweep(Exec* E, int s) {
   const Plan& P = *E->plan;
@@ -608,7 +652,7 @@ static int launch_sweep_member(Exec* E, int s) {
   const StepTimer t(E, s);
   if (t.rc != CTN_OK) return t.rc;
   const SweepDesc& sd = E->forms.sweep;
-  const int rc = sd.small ? (sd.two ? launch_sweep_small<true>(E, s) : launch_sweep_small<false>(E, s))
+  const int rc = sd.small ? (sd.f64 ? launch_sweep_small_f64(E, s) : sd.two ? launch_sweep_small<true>(E, s) : launch_sweep_small<false>(E, s))
                           : sd.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
   return rc != CTN_OK ? rc : t.end();
 }

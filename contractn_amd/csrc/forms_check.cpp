@@ -5,10 +5,12 @@
 //
 // Every argument is one setting: the networks in flight (R, default 1), the chip's CUs (CU, default 256) and development
 // switches by the names of their environment variables without the CTN_ prefix (ZIP, ZIPQ, ZIPL, ZIPL_MP, ZIPL_MAX_R, ZIPL64,
-// ZIP128, ZIPM64, ZIP512, CPLX, SWEEP, SWEEP64, SWEEP_SMALL, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
+// ZIP128, ZIPM64, ZIP512, CPLX, SWEEP, SWEEP64, SWEEP_SMALL, SWEEP_SMALL64, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
 // environment is not read.  ALIAS_LD=<n> is no switch but a change to the PLAN, for the one rule of the sweep matchers that
 // no planner-made layout reaches: the result of the run that sweep_small_match finds is moved onto the run's input in the
 // workspace, with rows n elements apart (a two-step run; n = the input's own row stride must stay taken, any other refused).
+// On a float64 plan the run is the one sweep_small_f64_match finds.  W_LDL=<n> likewise: the l stride of every core of that
+// float64 run becomes n (dense network inputs never have an odd one; the cores' own stride must stay taken).
 // For every plan and every setting one line goes to stdout with everything an executor would
 // decide when it is created:
 //
@@ -16,7 +18,7 @@
 //     forms=[<step>:<ctn_step_form>/zu<zu>/zm<zm>,..] lat=[<step>:mp<mp>/prev<0|1>/next<0|1>/buf<0|1>,..] cplx=[<sp>+<step>,..]
 //     partials=<n per step,..> off=<per step,..> slots=<n> scratch=<n>
 //     bufs=slab:<n>,fold:<n>,zl:<n>,group:<n>,sweep:<a>/<s>/<z>/<l>/<e>,tabs:<n>
-//     sweep=[<member steps,..>]<f32|f64|small2|small1|-> ares=[<step>:<ntw>,..] dot=[<step>,..] groups=[<head>:<len>,..]
+//     sweep=[<member steps,..>]<f32|f64|small2|small1|small2f64|-> ares=[<step>:<ntw>,..] dot=[<step>,..] groups=[<head>:<len>,..]
 //     side=[<tensor>:<buffer>,..]x<bytes>x<buffers> ok | <the invariant that failed>
 //
 // and these invariants are checked on each: a step's descriptor is on exactly under its role; an absorbed step is
@@ -35,7 +37,7 @@
 
 using namespace ctn;
 
-struct Setting { int R = 1, cu = 256, alias_ld = 0; DevSwitches sw; };
+struct Setting { int R = 1, cu = 256, alias_ld = 0, w_ldl = 0; DevSwitches sw; };
 
 static bool parse_setting(const char* arg, Setting* out) {
   std::string s(arg);
@@ -48,6 +50,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     if (key == "R") out->R = v;
     else if (key == "CU") out->cu = v;
     else if (key == "ALIAS_LD") out->alias_ld = v;
+    else if (key == "W_LDL") out->w_ldl = v;
     else if (key == "ZIP") d.zip = v;
     else if (key == "ZIPQ") d.zipq = v;
     else if (key == "ZIPL") d.zipl = v;
@@ -61,6 +64,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     else if (key == "SWEEP") d.sweep = v;
     else if (key == "SWEEP64") d.sweep64 = v;
     else if (key == "SWEEP_SMALL") d.sweep_small = v;
+    else if (key == "SWEEP_SMALL64") d.sweep_small64 = v;
     else if (key == "GROUP") d.group = v;
     else if (key == "ARES") d.ares = v;
     else if (key == "ARES_NTW") d.ares_ntw = v;
@@ -151,7 +155,7 @@ static void print_line(int plan, int set, const Plan& P, const FusedForms& F) {
          "side=[%s]x%lldx%d %s\n",
          plan, set, roles.c_str(), forms.c_str(), lat.c_str(), cplx.c_str(), partials.c_str(), offs.c_str(), (long long)F.part_slots,
          (long long)F.scratch_need, F.slab_elems, F.fold_elems, (long long)F.zl_slab_elems, F.group_args, F.sweep_a, F.sweep_s,
-         F.sweep_z, F.sweep_l, F.sweep_e, F.cplx_tabs.size(), sweep.c_str(), !F.sweep.on ? "-" : F.sweep.small ? (F.sweep.two ? "small2" : "small1") : F.sweep.f64 ? "f64" : "f32",
+         F.sweep_z, F.sweep_l, F.sweep_e, F.cplx_tabs.size(), sweep.c_str(), !F.sweep.on ? "-" : F.sweep.small ? (F.sweep.f64 ? "small2f64" : F.sweep.two ? "small2" : "small1") : F.sweep.f64 ? "f64" : "f32",
          ares.c_str(), dot.c_str(), groups.c_str(), side.c_str(), (long long)F.zqp_side_bytes, F.zqp_side_bufs,
          invariants(P, F).c_str());
 }
@@ -199,7 +203,13 @@ int main(int argc, char** argv) {
       // (a small-bond sweep that is asked for takes a chain plan from the chain walker: the executor's own first decision)
       Plan Q = sweep_small_unchains(P, sets[j].sw) ? unchained(P) : P;
       SweepDesc sd;
-      if (sets[j].alias_ld > 0 && sweep_small_match(Q, &sd) && sd.two && sd.idIn >= Q.n_inputs) {
+      const bool found = Q.dtype == CTN_F64 ? sweep_small_f64_match(Q, &sd) : sweep_small_match(Q, &sd);
+      if (sets[j].w_ldl > 0 && found && sd.f64)
+        for (size_t i = 0; i < sd.ids.size(); i += 2) {
+          Tensor& core = Q.tensors[sd.ids[i]];
+          for (int64_t& st : core.strides) if (st == sd.ldWl) st = sets[j].w_ldl;
+        }
+      if (sets[j].alias_ld > 0 && found && sd.two && sd.idIn >= Q.n_inputs) {
         Tensor& out = Q.tensors[Q.steps[sd.steps.back()].out];
         out.ws_offset = Q.tensors[sd.idIn].ws_offset;
         for (int64_t& st : out.strides) if (st != 1) st = sets[j].alias_ld;

@@ -59,7 +59,8 @@ struct SweepDesc {
   int idIn = -1;
   std::vector<int32_t> ids;
   // small bonds (kernels_sweep_small.h, float32): `two` - the members are the 2 S steps of S two-step sites, as in
-  // float64; else the S epilogue-summed steps.  ids and idIn are filled in both shapes.
+  // float64; else the S epilogue-summed steps.  ids and idIn are filled in both shapes.  small && f64: the float64 form of
+  // kernels_sweep_small_f64.h, always `two`.
   bool small = false, two = false;
 };
 // A full dot of a tensor with a transposed one (k_dot_tr), found on the plan's tables
@@ -268,9 +269,16 @@ static constexpr bool kSweepF64Default = false;
 // keeps a float32 site as two steps too while its epilogue-summed step would be small (plan.cpp: M >= 64, N >= 32, K >= 8,
 // M N >= 65536): any bond 8 ... 64 that is a multiple of 4, every stride of E, E' and W a multiple of 4 (16-byte accesses
 // of the state's rows), x rows of any stride >= |p|.
+// `small` with `small_dtype` CTN_F64: the float64 pair at a small bond, as one site of k_sweep_small_f64
+// (kernels_sweep_small_f64.h): the same bonds, x rows of any stride >= |p| (8-byte loads), and every stride of E, E' and W
+// even.  Why, stride by stride - the kernel's own accesses are all 8-byte: ldC (E') because k_sweep64_finish<double> rewrites
+// the result's rows as double2; ldA (E) because a member's E is the E' of the site before (cur.ldA == last.ldC) and the run's
+// input may be the very region its result lands on, with the same row stride (the aliasing rule below) - one parity for
+// both; ldWl and ldWp so that each 128-byte run that the 16 lanes of a group read of a core starts 16-byte aligned, as
+// k_sweep_f64's own condition has it (a bond-64 plan is refused by both kernels or by neither on its strides).
 struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
-inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, bool small = false) {
-  if (P.dtype != (small ? CTN_F32 : CTN_F64) || sb + 1 >= P.n_steps) return false;   // a step must follow the last member
+inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, bool small = false, int small_dtype = CTN_F32) {
+  if (P.dtype != (small ? small_dtype : CTN_F64) || sb + 1 >= P.n_steps) return false;   // a step must follow the last member
   const Step& a = P.steps[sa];
   const Step& b = P.steps[sb];
   // (small: whichever kernels the planner gave the two steps - at a few rows the GEMM is a streaming step itself; what the
@@ -306,8 +314,10 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, b
   const int64_t ldA = tE.strides[1 - el], ldC = tO.strides[axis(tO, lb)], ldX = tX.strides[axis(tX, lb)];
   const int64_t ldWl = tW.strides[axis(tW, ll)], ldWp = tW.strides[axis(tW, lp)];
   if (ldA < D || ldC < D || ldX < Pd || ldWl <= 0 || ldWp <= 0) return false;
-  if (small ? ((ldA | ldC | ldWl | ldWp) & 3) != 0 : ((ldA | ldC | ldX | ldWl | ldWp) & 1) != 0) return false;
-  if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;   // a lane's offsets into a core: 32 bits, in bytes
+  if (small ? ((ldA | ldC | ldWl | ldWp) & (small_dtype == CTN_F64 ? 1 : 3)) != 0 : ((ldA | ldC | ldX | ldWl | ldWp) & 1) != 0) return false;
+  // a lane's offsets into a core: 32 bits, in bytes.  (8-byte elements: the largest a lane of k_sweep_small_f64 forms is
+  // (3 ldWl + 3 ldWp + D) 8 < 2^28 x 8 = 2^31; the rows 16 G + 4 e go into the 64-bit base.)
+  if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;
   sh->idE = idE; sh->idW = idW; sh->idX = idX; sh->idOut = b.out;
   sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = (int)D; sh->Pd = (int)Pd;
   return true;
@@ -316,7 +326,7 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, b
 // The longest run of such pairs, each taking the result of the one before as its E.  The two safety rules are those of
 // sweep_match: nothing that is launched may lie between two members, and the run's result may overlap its input only as
 // the same region with the same row stride.
-inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
+inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false, int small_dtype = CTN_F32) {
   auto next_launched = [&](int s) { do ++s; while (s < P.n_steps && P.steps[s].kernel == CTN_KERNEL_FUSED); return s; };
   std::vector<int> best;
   std::vector<int32_t> best_ids;
@@ -325,14 +335,14 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
   for (int s0 = 0; s0 < P.n_steps; ++s0) {
     Sweep64Site first, cur, last;
     int sb = next_launched(s0);
-    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first, small)) continue;
+    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first, small, small_dtype)) continue;
     std::vector<int> run{s0, sb};
     std::vector<int32_t> ids{first.idW, first.idX};
     last = first;
     for (;;) {
       const int na = next_launched(run.back());
       const int nb = na < P.n_steps ? next_launched(na) : na;
-      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur, small) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
+      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur, small, small_dtype) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
           cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC)
         break;
       run.push_back(na); run.push_back(nb);
@@ -354,7 +364,7 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
       if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
     }
   }
-  d->on = true; d->f64 = !small; d->small = small; d->two = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
+  d->on = true; d->f64 = !small || small_dtype == CTN_F64; d->small = small; d->two = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
   d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
   d->J = (int)((best_first.M + kFormSWR - 1) / kFormSWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
   return true;
@@ -384,13 +394,42 @@ inline bool sweep_small_asked(const Plan& P, const DevSwitches& sw) {
   return sw.sweep != 0 && P.stabilize && (sw.sweep_small == 1 || (kSweepSmallDefault && sw.sweep_small != 0));
 }
 
+// Is k_sweep_small_f64 taken without CTN_SWEEP_SMALL64=1 wherever sweep_small_f64_match takes a run?  Decided by measurement
+// (DESIGN sections 10 and 11, item 3c): tools/sweep_small_timing.py --dtype f64 has to show the one launch ahead of the
+// per-site launches by more than the larger spread at every one of its shapes, and the float64 small-bond GPU suite has to
+// be green with CTN_SWEEP_SMALL64=1.
+static constexpr bool kSweepSmallF64Default = false;
+
+// A float64 batched MPS of bond 8 ... 64 (kernels_sweep_small_f64.h): the longest run of two-step sites - the one shape a
+// float64 plan has.  sweep64_match keeps its two safety rules.  At most kFormSweepMaxSites sites.
+inline bool sweep_small_f64_match(const Plan& P, SweepDesc* d) {
+  if (P.dtype != CTN_F64) return false;
+  return sweep64_match(P, d, true, CTN_F64) && (int)(d->steps.size() / 2) <= kFormSweepMaxSites;
+}
+
+// Is it asked for on this plan?  Only on request (CTN_SWEEP_SMALL64=1) while kSweepSmallF64Default is off, never against
+// CTN_SWEEP=0 or CTN_SWEEP64=0, never on a float32 plan.
+inline bool sweep_small_f64_asked(const Plan& P, const DevSwitches& sw) {
+  return P.dtype == CTN_F64 && sw.sweep != 0 && sw.sweep64 != 0 && P.stabilize &&
+         (sw.sweep_small64 == 1 || (kSweepSmallF64Default && sw.sweep_small64 != 0));
+}
+
+// Does k_sweep_f64 take the plan (CTN_SWEEP=1, bond 64 ... 512, MFMA-sized steps)?  Its run is never the small form's.
+inline bool sweep64_takes(const Plan& P, const DevSwitches& sw, SweepDesc* d) {
+  return P.dtype == CTN_F64 && sw.sweep != 0 && P.stabilize && sw.sweep64 != 0 && (sw.sweep == 1 || kSweepF64Default) &&
+         sweep64_match(P, d) && (int)d->steps.size() <= 2 * kFormSweepMaxSites;
+}
+
 // A chain plan (Plan::chain: every step small) is walked whole by the chain walker and has no fused form - most
 // small-bond classifiers with a batch of a few dozen are such plans.  A small-bond sweep that is asked for and matches
 // takes the plan from the walker: the executor (and forms_check) then works on a copy whose steps are launches of their
 // own again, with the slot counts and collapse flags the planner gave them before it marked the plan.
+// The float64 form (CTN_SWEEP_SMALL64=1) does the same, where k_sweep_f64 would not take the un-chained plan.
 inline bool sweep_small_unchains(const Plan& P, const DevSwitches& sw) {
-  SweepDesc d;
-  return P.chain && sweep_small_asked(P, sw) && sweep_small_match(P, &d);
+  if (!P.chain) return false;
+  SweepDesc d, d64, k64;
+  if (sweep_small_asked(P, sw) && sweep_small_match(P, &d)) return true;
+  return sweep_small_f64_asked(P, sw) && sweep_small_f64_match(P, &d64) && !sweep64_takes(P, sw, &k64);
 }
 inline Plan unchained(const Plan& P) {
   Plan Q = P;
@@ -728,7 +767,8 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.ares_ntw[s] = ares_match(P, s, R, n_cu, sw);
       if (F.ares_ntw[s] && ares_avec(P, s)) F.ares_ntw[s] |= 1 << 16;
     }
-  // a sweep: at least half a chip of row blocks, or CTN_SWEEP=1; at the small bonds only on request (CTN_SWEEP_SMALL=1)
+  // a sweep: at least half a chip of row blocks, or CTN_SWEEP=1; at the small bonds only on request (CTN_SWEEP_SMALL=1,
+  // float64: CTN_SWEEP_SMALL64=1)
   if (sw.sweep != 0 && P.stabilize) {
     SweepDesc sd;
     // (bonds up to 128: the per-site launches are a few microseconds of latency each whatever the batch - always)
@@ -738,8 +778,7 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       for (int s : sd.steps) { F.sweep_ids.push_back(P.steps[s].rhs); F.sweep_ids.push_back(P.steps[s].lhs2); }
       F.sweep_a = nrec; F.sweep_s = nrec; F.sweep_z = (size_t)R * S; F.sweep_l = nrec;
       F.sweep = sd;
-    } else if (P.dtype == CTN_F64 && sw.sweep64 != 0 && (sw.sweep == 1 || kSweepF64Default) && sweep64_match(P, &sd) &&
-               (int)sd.steps.size() <= 2 * kFormSweepMaxSites) {
+    } else if (sweep64_takes(P, sw, &sd)) {
       // float64 (k_sweep_f64): the run's 2 S steps are all members - a GEMM and a streaming step per site
       const size_t T = sd.steps.size(), nrec = (size_t)R * (T / 2) * sd.J;
       F.sweep_ids = sd.ids;
@@ -752,6 +791,13 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.sweep_ids = ss.ids;
       F.sweep_a = (ss.two ? 2 : 1) * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * ss.steps.size();
       F.sweep = ss;
+    } else if (SweepDesc sf; sweep_small_f64_asked(P, sw) && sweep_small_f64_match(P, &sf)) {
+      // small bonds in float64 (k_sweep_small_f64, CTN_SWEEP_SMALL64=1), only where k_sweep_f64 did not take the plan: the
+      // records of the two-step shape above
+      const size_t S = sf.steps.size() / 2, nrec = (size_t)R * S * sf.J;
+      F.sweep_ids = sf.ids;
+      F.sweep_a = 2 * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * sf.steps.size();
+      F.sweep = sf;
     }
     for (int s : F.sweep.steps) {
       F.sweep_role[s] = s == F.sweep.steps.back() ? 2 : 1;

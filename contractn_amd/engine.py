@@ -48,7 +48,7 @@ ABI_SYMBOLS = (
 )
 # ctn_step_form (ctn_exec_step_form): the fused zipper-pair kernel a step ran as
 STEP_FORMS = {0: None, 1: "k_zip_f32", 2: "k_zipq_f32", 3: "k_zip64_f32", 4: "k_zip128_f32", 5: "k_zipm64_f32", 6: "k_zip_f64", 7: "k_zipqp_f32",
-              8: "k_zip_lat_f64", 9: "k_zip512_f32"}
+              8: "k_zip_lat_f64", 9: "k_zip512_f32", 10: "k_sweep_small_f32", 11: "k_sweep_small_f64"}
 # ctn_walk_form (ctn_exec_walk_form): how a plan of small steps is walked in one launch
 WALK_FORMS = {0: None, 1: "k_chain", 2: "k_chain_lds"}
 GRAD_SCRATCH = 512          # doubles of scratch ctn_grad_seed needs (CTN_GRAD_SCRATCH)

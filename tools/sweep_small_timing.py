@@ -11,9 +11,13 @@ and ``ahead``: whether the switch's median is below the unset one by more than t
 asked for.  The raw lines go to --out (default profiles/sweep_small_ab.json, a JSON list).  This tool checks no values:
 tests/test_gpu_sweep_small_elements.py is the correctness check.
 
+``--dtype f64`` measures the float64 form instead (k_sweep_small_f64, CTN_SWEEP_SMALL64=1; the cases of
+tests/sweep_cases_small_f64.py, default --out profiles/sweep_small_f64_ab.json): the same six shapes, sites, rounds and
+``ahead`` rule; tests/test_gpu_sweep_small_f64.py is its correctness check.
+
 Run it under a time limit of its own (`timeout -k 10 420 python tools/sweep_small_timing.py`): it takes about a minute.
 
-    python tools/sweep_small_timing.py [--sites 100] [--rounds 5] [--reps 300] [--warmup 5] [--out FILE]
+    python tools/sweep_small_timing.py [--dtype f32|f64] [--sites 100] [--rounds 5] [--reps 300] [--warmup 5] [--out FILE]
 """
 import argparse
 import json
@@ -30,18 +34,26 @@ import torch  # noqa: E402
 
 from contractn_amd import einsum as E  # noqa: E402
 from tests import sweep_cases_small as C  # noqa: E402
+from tests import sweep_cases_small_f64 as C64  # noqa: E402
 
 SHAPES = [(16, 2, 256), (32, 2, 256), (32, 2, 1024), (32, 2, 4096), (64, 2, 256), (48, 4, 1024)]      # (D, P, B)
 
 
-def executor(net, switch):
-    """An executor created with CTN_SWEEP_SMALL=`switch` (None: unset); the switches are read at creation only."""
-    os.environ.pop("CTN_SWEEP_SMALL", None)
+# per --dtype: the switch, the element type, torch's, the operands, and whether the planner keeps a site as two steps
+DTYPES = {
+    "f32": ("CTN_SWEEP_SMALL", np.float32, torch.float32, lambda net: C.random_operands(net, 0), C.is_two),
+    "f64": ("CTN_SWEEP_SMALL64", np.float64, torch.float64, lambda net: C64.random_operands64(net, 0), lambda net: True),
+}
+
+
+def executor(net, switch, key="CTN_SWEEP_SMALL", dtype=np.float32):
+    """An executor created with `key`=`switch` (None: unset); the switches are read at creation only."""
+    os.environ.pop(key, None)
     if switch is not None:
-        os.environ["CTN_SWEEP_SMALL"] = switch
+        os.environ[key] = switch
     E.clear_caches()
-    bc = E.BatchedContraction(net.einsum_str, net.shapes, np.float32, optimize=net.path, replicas=1)
-    os.environ.pop("CTN_SWEEP_SMALL", None)
+    bc = E.BatchedContraction(net.einsum_str, net.shapes, dtype, optimize=net.path, replicas=1)
+    os.environ.pop(key, None)
     return bc
 
 
@@ -55,14 +67,18 @@ def one_round(bc, ins, outs, reps):
     return float(np.median(wall))
 
 
-def measure(D, P, B, sites, rounds, reps, warmup):
+def measure(D, P, B, sites, rounds, reps, warmup, dtype="f32"):
+    key, np_dtype, torch_dtype, operands, is_two = DTYPES[dtype]
+    on = key + "=1"
     net = C.Net(D, P, B, sites, "plr", "produced")
-    dev_ops = [torch.from_numpy(np.ascontiguousarray(o)).cuda() for o in C.random_operands(net, 0)]
+    dev_ops = [torch.from_numpy(np.ascontiguousarray(o)).cuda() for o in operands(net)]
     torch.cuda.synchronize()
     ins = [o.data_ptr() for o in dev_ops]
-    modes = {"CTN_SWEEP_SMALL=1": executor(net, "1"), "unset": executor(net, None)}
-    outs = {k: torch.empty(net.out_shape, dtype=torch.float32, device="cuda") for k in modes}
-    res = {"shape": {"D": D, "P": P, "B": B, "sites": sites}, "two_step_plan": C.is_two(net)}
+    modes = {on: executor(net, "1", key, np_dtype), "unset": executor(net, None, key, np_dtype)}
+    outs = {k: torch.empty(net.out_shape, dtype=torch_dtype, device="cuda") for k in modes}
+    res = {"shape": {"D": D, "P": P, "B": B, "sites": sites}, "two_step_plan": bool(is_two(net))}
+    if dtype != "f32":
+        res["dtype"] = dtype
     try:
         for k, bc in modes.items():
             for _ in range(warmup):
@@ -83,9 +99,9 @@ def measure(D, P, B, sites, rounds, reps, warmup):
             res[k] = {"round_ms": [round(v, 5) for v in per[k]], "median_ms": float(np.median(ms)), "spread_ms": float(ms.max() - ms.min()),
                       "one_launch": (16, D * P) in bc.executor.step_tiles(), "launched_steps": int(np.count_nonzero(step_ms > 0)),
                       "walk_form": int(bc.executor.walk_form()) if hasattr(bc.executor, "walk_form") else None}
-        a, b = res["CTN_SWEEP_SMALL=1"], res["unset"]
+        a, b = res[on], res["unset"]
         res["ahead"] = bool(b["median_ms"] - a["median_ms"] > max(a["spread_ms"], b["spread_ms"]))
-        same = torch.allclose(outs["CTN_SWEEP_SMALL=1"], outs["unset"], rtol=1e-3, atol=1e-5 * float(outs["unset"].abs().max()))
+        same = torch.allclose(outs[on], outs["unset"], rtol=1e-3, atol=1e-5 * float(outs["unset"].abs().max()))
         res["results_agree_1e-3"] = bool(same)
     finally:
         for bc in modes.values():
@@ -100,13 +116,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_small_ab.json"))
+    ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "sweep_small_ab.json" if a.dtype == "f32" else "sweep_small_f64_ab.json")
     if not torch.cuda.is_available():
         sys.exit("sweep_small_timing: no GPU - a time is measured on the device or not at all")
     lines = []
     for D, P, B in SHAPES:
-        lines.append(measure(D, P, B, a.sites, a.rounds, a.reps, a.warmup))
+        lines.append(measure(D, P, B, a.sites, a.rounds, a.reps, a.warmup, a.dtype))
         print(json.dumps(lines[-1]), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
