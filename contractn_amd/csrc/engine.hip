@@ -55,7 +55,6 @@
 #include "kernels_sweep.h"
 #include "kernels_sweep_f64.h"
 #include "kernels_sweep_small.h"
-#include "kernels_sweep_small_f64.h"
 #include "kernels_mfma_lat.h"
 #include "kernels_stream.h"
 #include "kernels_chain.h"
@@ -474,6 +473,26 @@ static void launch_group(Exec* E, const LeafGroup& G) {
   else launch_stream_group<double>(G.vw, G.u, g, E->stream, E->d_group_args + G.off);
 }
 
+// the scale bookkeeping behind a sweep kernel that leaves the records of k_sweep_f64 (rec_a, rec_e): the members' rescale
+// factors, then the result's rows at their common scale.  <T, TWO>: the rows' element type; two member steps per site or one
+template <typename T, bool TWO>
+static void launch_sweep64_finish(Exec* E, int s) {
+  const Plan& P = *E->plan;
+  const Step& st = P.steps[s];
+  const int R = E->R;
+  const SweepDesc& sd = E->forms.sweep;
+  const int S = (int)sd.steps.size() / (TWO ? 2 : 1);
+  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
+  hipLaunchKernelGGL(k_sweep64_z<TWO>, dim3((unsigned)sd.steps.size(), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
+                     (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
+  Sweep64Finish f{};
+  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
+  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
+  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
+  hipLaunchKernelGGL((k_sweep64_finish<T, TWO>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+}
+
 // the last member of a float64 sweep: 2 S member steps, S sites
 static int launch_sweep64(Exec* E, int s) {
   const Plan& P = *E->plan;
@@ -502,42 +521,34 @@ static int launch_sweep64(Exec* E, int s) {
     else CTN_SWEEP64_LAUNCH(512);
 #undef CTN_SWEEP64_LAUNCH
   }
-  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
-  hipLaunchKernelGGL(k_sweep64_z<true>, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
-                     (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
-  Sweep64Finish f{};
-  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
-  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
-  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
-  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
-  hipLaunchKernelGGL((k_sweep64_finish<double, true>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+  launch_sweep64_finish<double, true>(E, s);
   return CTN_OK;
 }
 
-// the last member of a small-bond sweep (CTN_SWEEP_SMALL=1): S sites of two member steps each (`two`) or of one
-template <bool TWO>
+// the last member of a small-bond sweep (float: CTN_SWEEP_SMALL=1, double: CTN_SWEEP_SMALL64=1): S sites of two member
+// steps each (`two`; double always) or of one
+template <typename T, bool TWO>
 static int launch_sweep_small(Exec* E, int s) {
   const Plan& P = *E->plan;
   const Step& st = P.steps[s];
   const int R = E->R;
   const SweepDesc& sd = E->forms.sweep;
-  const int S = (int)sd.steps.size() / (TWO ? 2 : 1);
   SweepSmallArgs w{};
   w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
-  w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M; w.D = sd.D;
+  w.idIn = sd.idIn; w.idOut = st.out; w.S = (int)sd.steps.size() / (TWO ? 2 : 1); w.J = sd.J; w.M = sd.M; w.D = sd.D;
   w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
   producer_partials(E, sd.idIn, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
   w.min_norm = P.min_norm;
   w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
-  E->launched_form[s] = CTN_FORM_SWEEP_SMALL;
+  E->launched_form[s] = sizeof(T) == 4 ? CTN_FORM_SWEEP_SMALL : CTN_FORM_SWEEP_SMALL_F64;
   report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns of C per wave, every site
   {
     const dim3 gs((unsigned)sd.J, (unsigned)R);
     const int DB = (sd.D + 15) / 16;
 #define CTN_SWEEP_SMALL_LAUNCH(BB)                                                                          \
     do {                                                                                                    \
-      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small_f32<BB, 4, TWO>), gs, dim3(64), 0, E->stream, w);   \
-      else hipLaunchKernelGGL((k_sweep_small_f32<BB, 2, TWO>), gs, dim3(64), 0, E->stream, w);              \
+      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small<T, BB, 4, TWO>), gs, dim3(64), 0, E->stream, w);    \
+      else hipLaunchKernelGGL((k_sweep_small<T, BB, 2, TWO>), gs, dim3(64), 0, E->stream, w);               \
     } while (0)
     if (DB == 1) CTN_SWEEP_SMALL_LAUNCH(1);
     else if (DB == 2) CTN_SWEEP_SMALL_LAUNCH(2);
@@ -545,59 +556,7 @@ static int launch_sweep_small(Exec* E, int s) {
     else CTN_SWEEP_SMALL_LAUNCH(4);
 #undef CTN_SWEEP_SMALL_LAUNCH
   }
-  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
-  const int T = (int)sd.steps.size();
-  hipLaunchKernelGGL(k_sweep64_z<TWO>, dim3((unsigned)T, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
-                     (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
-  Sweep64Finish f{};
-  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
-  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
-  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
-  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
-  hipLaunchKernelGGL((k_sweep64_finish<float, TWO>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
-  return CTN_OK;
-}
-
-// the last member of a float64 small-bond sweep (CTN_SWEEP_SMALL64=1): S sites of two member steps each; the bookkeeping
-// launches are launch_sweep64's
-static int launch_sweep_small_f64(Exec* E, int s) {
-  const Plan& P = *E->plan;
-  const Step& st = P.steps[s];
-  const int R = E->R;
-  const SweepDesc& sd = E->forms.sweep;
-  const int S = (int)sd.steps.size() / 2;
-  SweepSmallArgs w{};
-  w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
-  w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M; w.D = sd.D;
-  w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
-  producer_partials(E, sd.idIn, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
-  w.min_norm = P.min_norm;
-  w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
-  E->launched_form[s] = CTN_FORM_SWEEP_SMALL_F64;
-  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns of C per wave, every site
-  {
-    const dim3 gs((unsigned)sd.J, (unsigned)R);
-    const int DB = (sd.D + 15) / 16;
-#define CTN_SWEEP_SMALL64_LAUNCH(BB)                                                                    \
-    do {                                                                                                \
-      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small_f64<BB, 4>), gs, dim3(64), 0, E->stream, w);    \
-      else hipLaunchKernelGGL((k_sweep_small_f64<BB, 2>), gs, dim3(64), 0, E->stream, w);               \
-    } while (0)
-    if (DB == 1) CTN_SWEEP_SMALL64_LAUNCH(1);
-    else if (DB == 2) CTN_SWEEP_SMALL64_LAUNCH(2);
-    else if (DB == 3) CTN_SWEEP_SMALL64_LAUNCH(3);
-    else CTN_SWEEP_SMALL64_LAUNCH(4);
-#undef CTN_SWEEP_SMALL64_LAUNCH
-  }
-  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
-  hipLaunchKernelGGL(k_sweep64_z<true>, dim3((unsigned)(2 * S), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
-                     (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
-  Sweep64Finish f{};
-  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
-  f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
-  f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
-  f.min_norm = P.stabilize ? P.min_norm : INFINITY;
-  hipLaunchKernelGGL((k_sweep64_finish<double, true>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
+  launch_sweep64_finish<T, TWO>(E, s);
   return CTN_OK;
 }
 
@@ -652,7 +611,7 @@ static int launch_sweep_member(Exec* E, int s) {
   const StepTimer t(E, s);
   if (t.rc != CTN_OK) return t.rc;
   const SweepDesc& sd = E->forms.sweep;
-  const int rc = sd.small ? (sd.f64 ? launch_sweep_small_f64(E, s) : sd.two ? launch_sweep_small<true>(E, s) : launch_sweep_small<false>(E, s))
+  const int rc = sd.small ? (sd.f64 ? launch_sweep_small<double, true>(E, s) : sd.two ? launch_sweep_small<float, true>(E, s) : launch_sweep_small<float, false>(E, s))
                           : sd.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
   return rc != CTN_OK ? rc : t.end();
 }

@@ -9,7 +9,7 @@
 // environment is not read.  ALIAS_LD=<n> is no switch but a change to the PLAN, for the one rule of the sweep matchers that
 // no planner-made layout reaches: the result of the run that sweep_small_match finds is moved onto the run's input in the
 // workspace, with rows n elements apart (a two-step run; n = the input's own row stride must stay taken, any other refused).
-// On a float64 plan the run is the one sweep_small_f64_match finds.  W_LDL=<n> likewise: the l stride of every core of that
+// On a float64 plan the run is the one the same matcher finds there.  W_LDL=<n> likewise: the l stride of every core of that
 // float64 run becomes n (dense network inputs never have an odd one; the cores' own stride must stay taken).
 // For every plan and every setting one line goes to stdout with everything an executor would
 // decide when it is created:
@@ -203,7 +203,7 @@ int main(int argc, char** argv) {
       // (a small-bond sweep that is asked for takes a chain plan from the chain walker: the executor's own first decision)
       Plan Q = sweep_small_unchains(P, sets[j].sw) ? unchained(P) : P;
       SweepDesc sd;
-      const bool found = Q.dtype == CTN_F64 ? sweep_small_f64_match(Q, &sd) : sweep_small_match(Q, &sd);
+      const bool found = sweep_small_match(Q, &sd);
       if (sets[j].w_ldl > 0 && found && sd.f64)
         for (size_t i = 0; i < sd.ids.size(); i += 2) {
           Tensor& core = Q.tensors[sd.ids[i]];

@@ -58,9 +58,9 @@ struct SweepDesc {
   bool f64 = false;
   int idIn = -1;
   std::vector<int32_t> ids;
-  // small bonds (kernels_sweep_small.h, float32): `two` - the members are the 2 S steps of S two-step sites, as in
-  // float64; else the S epilogue-summed steps.  ids and idIn are filled in both shapes.  small && f64: the float64 form of
-  // kernels_sweep_small_f64.h, always `two`.
+  // small bonds (kernels_sweep_small.h): `two` - the members are the 2 S steps of S two-step sites, as in float64; else
+  // the S epilogue-summed steps (float32 only).  ids and idIn are filled in both shapes.  small && f64: k_sweep_small<double>,
+  // always `two`.
   bool small = false, two = false;
 };
 // A full dot of a tensor with a transposed one (k_dot_tr), found on the plan's tables
@@ -163,7 +163,7 @@ static constexpr bool kCplxDefault = false;
 
 // Is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
 // offset tables: E row-major [b][l], W[l][p][r] with r unit-stride, x[b][p] with p unit-stride, result rows [b][r].
-// `small`: as one site of k_sweep_small_f32 instead - any bond 8 ... 64 that is a multiple of 4, x rows of any stride >= |p|.
+// `small`: as one site of k_sweep_small<float> instead - any bond 8 ... 64 that is a multiple of 4, x rows of any stride >= |p|.
 struct SweepShape { int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
 inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh, bool small = false) {
   const Step& st = P.steps[s];
@@ -265,20 +265,20 @@ static constexpr bool kSweepF64Default = false;
 // the pair as one site?  Matched on the tensors' labels, dims and strides: E and E' row-major [b][.], r unit-stride in W,
 // p unit-stride in x, every stride even (16-byte accesses).  The layout the planner gave C does not matter: C is never
 // written.
-// `small`: the same pair in float32 at a small bond, as one site of k_sweep_small_f32 (kernels_sweep_small.h) - the planner
+// `small`: the same pair in float32 at a small bond, as one site of k_sweep_small<float> (kernels_sweep_small.h) - the planner
 // keeps a float32 site as two steps too while its epilogue-summed step would be small (plan.cpp: M >= 64, N >= 32, K >= 8,
 // M N >= 65536): any bond 8 ... 64 that is a multiple of 4, every stride of E, E' and W a multiple of 4 (16-byte accesses
 // of the state's rows), x rows of any stride >= |p|.
-// `small` with `small_dtype` CTN_F64: the float64 pair at a small bond, as one site of k_sweep_small_f64
-// (kernels_sweep_small_f64.h): the same bonds, x rows of any stride >= |p| (8-byte loads), and every stride of E, E' and W
-// even.  Why, stride by stride - the kernel's own accesses are all 8-byte: ldC (E') because k_sweep64_finish<double> rewrites
+// `small` on a float64 plan: the float64 pair at a small bond, as one site of k_sweep_small<double>: the same bonds, x
+// rows of any stride >= |p| (8-byte loads), and every stride of E, E' and W even.  (`small` takes the plan's own type,
+// float32 or float64 and nothing else.)  Why, stride by stride - the kernel's own accesses are all 8-byte: ldC (E') because k_sweep64_finish<double> rewrites
 // the result's rows as double2; ldA (E) because a member's E is the E' of the site before (cur.ldA == last.ldC) and the run's
 // input may be the very region its result lands on, with the same row stride (the aliasing rule below) - one parity for
 // both; ldWl and ldWp so that each 128-byte run that the 16 lanes of a group read of a core starts 16-byte aligned, as
 // k_sweep_f64's own condition has it (a bond-64 plan is refused by both kernels or by neither on its strides).
 struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
-inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, bool small = false, int small_dtype = CTN_F32) {
-  if (P.dtype != (small ? small_dtype : CTN_F64) || sb + 1 >= P.n_steps) return false;   // a step must follow the last member
+inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, bool small = false) {
+  if ((P.dtype != CTN_F64 && !(small && P.dtype == CTN_F32)) || sb + 1 >= P.n_steps) return false;   // a step must follow the last member
   const Step& a = P.steps[sa];
   const Step& b = P.steps[sb];
   // (small: whichever kernels the planner gave the two steps - at a few rows the GEMM is a streaming step itself; what the
@@ -314,8 +314,8 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, b
   const int64_t ldA = tE.strides[1 - el], ldC = tO.strides[axis(tO, lb)], ldX = tX.strides[axis(tX, lb)];
   const int64_t ldWl = tW.strides[axis(tW, ll)], ldWp = tW.strides[axis(tW, lp)];
   if (ldA < D || ldC < D || ldX < Pd || ldWl <= 0 || ldWp <= 0) return false;
-  if (small ? ((ldA | ldC | ldWl | ldWp) & (small_dtype == CTN_F64 ? 1 : 3)) != 0 : ((ldA | ldC | ldX | ldWl | ldWp) & 1) != 0) return false;
-  // a lane's offsets into a core: 32 bits, in bytes.  (8-byte elements: the largest a lane of k_sweep_small_f64 forms is
+  if (small ? ((ldA | ldC | ldWl | ldWp) & (P.dtype == CTN_F64 ? 1 : 3)) != 0 : ((ldA | ldC | ldX | ldWl | ldWp) & 1) != 0) return false;
+  // a lane's offsets into a core: 32 bits, in bytes.  (8-byte elements: the largest a lane of k_sweep_small<double> forms is
   // (3 ldWl + 3 ldWp + D) 8 < 2^28 x 8 = 2^31; the rows 16 G + 4 e go into the 64-bit base.)
   if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;
   sh->idE = idE; sh->idW = idW; sh->idX = idX; sh->idOut = b.out;
@@ -326,7 +326,7 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, b
 // The longest run of such pairs, each taking the result of the one before as its E.  The two safety rules are those of
 // sweep_match: nothing that is launched may lie between two members, and the run's result may overlap its input only as
 // the same region with the same row stride.
-inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false, int small_dtype = CTN_F32) {
+inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
   auto next_launched = [&](int s) { do ++s; while (s < P.n_steps && P.steps[s].kernel == CTN_KERNEL_FUSED); return s; };
   std::vector<int> best;
   std::vector<int32_t> best_ids;
@@ -335,14 +335,14 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false, int s
   for (int s0 = 0; s0 < P.n_steps; ++s0) {
     Sweep64Site first, cur, last;
     int sb = next_launched(s0);
-    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first, small, small_dtype)) continue;
+    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first, small)) continue;
     std::vector<int> run{s0, sb};
     std::vector<int32_t> ids{first.idW, first.idX};
     last = first;
     for (;;) {
       const int na = next_launched(run.back());
       const int nb = na < P.n_steps ? next_launched(na) : na;
-      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur, small, small_dtype) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
+      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur, small) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
           cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC)
         break;
       run.push_back(na); run.push_back(nb);
@@ -364,54 +364,43 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false, int s
       if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
     }
   }
-  d->on = true; d->f64 = !small || small_dtype == CTN_F64; d->small = small; d->two = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
+  d->on = true; d->f64 = P.dtype == CTN_F64; d->small = small; d->two = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
   d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
   d->J = (int)((best_first.M + kFormSWR - 1) / kFormSWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
   return true;
 }
 
-// Is k_sweep_small_f32 taken without CTN_SWEEP_SMALL=1 wherever sweep_small_match takes a run?  Decided by measurement
+// Is k_sweep_small<float> taken without CTN_SWEEP_SMALL=1 wherever sweep_small_match takes a run?  Decided by measurement
 // (DESIGN sections 10 and 11): tools/sweep_small_timing.py has to show the one launch ahead of the per-site launches by
 // more than the larger spread at every one of its shapes, and the small-bond GPU suite has to be green with CTN_SWEEP_SMALL=1.
 static constexpr bool kSweepSmallDefault = false;
-
-// A float32 batched MPS of bond 8 ... 64 (kernels_sweep_small.h) in either shape the planner gives its sites: the longest run
-// of two-step sites (sweep64_match on the float32 plan) or of epilogue-summed steps (sweep_match at the small bonds),
-// whichever walks more sites.  Both matchers keep their two safety rules: nothing launched between members, and the
-// run's result overlaps its input only as the same region with the same row stride.  At most kFormSweepMaxSites sites.
-inline bool sweep_small_match(const Plan& P, SweepDesc* d) {
-  if (P.dtype != CTN_F32) return false;
-  SweepDesc two, one;
-  const bool m2 = sweep64_match(P, &two, true), m1 = sweep_match(P, &one, true);
-  if (!m1 && !m2) return false;
-  *d = (m2 && (!m1 || two.steps.size() / 2 >= one.steps.size())) ? two : one;
-  return (int)(d->two ? d->steps.size() / 2 : d->steps.size()) <= kFormSweepMaxSites;
-}
-
-// Is the small-bond sweep asked for on this plan?  Only on request (CTN_SWEEP_SMALL=1) while kSweepSmallDefault is off, and
-// never against CTN_SWEEP=0.
-inline bool sweep_small_asked(const Plan& P, const DevSwitches& sw) {
-  return sw.sweep != 0 && P.stabilize && (sw.sweep_small == 1 || (kSweepSmallDefault && sw.sweep_small != 0));
-}
-
-// Is k_sweep_small_f64 taken without CTN_SWEEP_SMALL64=1 wherever sweep_small_f64_match takes a run?  Decided by measurement
+// Is k_sweep_small<double> taken without CTN_SWEEP_SMALL64=1 wherever sweep_small_match takes a run?  Decided by measurement
 // (DESIGN sections 10 and 11, item 3c): tools/sweep_small_timing.py --dtype f64 has to show the one launch ahead of the
 // per-site launches by more than the larger spread at every one of its shapes, and the float64 small-bond GPU suite has to
 // be green with CTN_SWEEP_SMALL64=1.
 static constexpr bool kSweepSmallF64Default = false;
 
-// A float64 batched MPS of bond 8 ... 64 (kernels_sweep_small_f64.h): the longest run of two-step sites - the one shape a
-// float64 plan has.  sweep64_match keeps its two safety rules.  At most kFormSweepMaxSites sites.
-inline bool sweep_small_f64_match(const Plan& P, SweepDesc* d) {
-  if (P.dtype != CTN_F64) return false;
-  return sweep64_match(P, d, true, CTN_F64) && (int)(d->steps.size() / 2) <= kFormSweepMaxSites;
+// A batched MPS of bond 8 ... 64 (kernels_sweep_small.h).  Float32, in either shape the planner gives its sites: the longest
+// run of two-step sites (sweep64_match on the float32 plan) or of epilogue-summed steps (sweep_match at the small bonds),
+// whichever walks more sites.  Float64: the longest run of two-step sites - the one shape a float64 plan has.  Both
+// matchers keep their two safety rules: nothing launched between members, and the run's result overlaps its input only
+// as the same region with the same row stride.  At most kFormSweepMaxSites sites.
+inline bool sweep_small_match(const Plan& P, SweepDesc* d) {
+  if (P.dtype != CTN_F32 && P.dtype != CTN_F64) return false;
+  SweepDesc two, one;
+  const bool m2 = sweep64_match(P, &two, true), m1 = P.dtype == CTN_F32 && sweep_match(P, &one, true);
+  if (!m1 && !m2) return false;
+  *d = (m2 && (!m1 || two.steps.size() / 2 >= one.steps.size())) ? two : one;
+  return (int)(d->two ? d->steps.size() / 2 : d->steps.size()) <= kFormSweepMaxSites;
 }
 
-// Is it asked for on this plan?  Only on request (CTN_SWEEP_SMALL64=1) while kSweepSmallF64Default is off, never against
-// CTN_SWEEP=0 or CTN_SWEEP64=0, never on a float32 plan.
-inline bool sweep_small_f64_asked(const Plan& P, const DevSwitches& sw) {
-  return P.dtype == CTN_F64 && sw.sweep != 0 && sw.sweep64 != 0 && P.stabilize &&
-         (sw.sweep_small64 == 1 || (kSweepSmallF64Default && sw.sweep_small64 != 0));
+// Is the small-bond sweep asked for on this plan?  Only on request while its type's default is off - float32:
+// CTN_SWEEP_SMALL=1, kSweepSmallDefault; float64: CTN_SWEEP_SMALL64=1, kSweepSmallF64Default, and not against CTN_SWEEP64=0;
+// neither switch reaches the other type - and never against CTN_SWEEP=0.
+inline bool sweep_small_asked(const Plan& P, const DevSwitches& sw) {
+  if (sw.sweep == 0 || !P.stabilize) return false;
+  if (P.dtype == CTN_F32) return sw.sweep_small == 1 || (kSweepSmallDefault && sw.sweep_small != 0);
+  return P.dtype == CTN_F64 && sw.sweep64 != 0 && (sw.sweep_small64 == 1 || (kSweepSmallF64Default && sw.sweep_small64 != 0));
 }
 
 // Does k_sweep_f64 take the plan (CTN_SWEEP=1, bond 64 ... 512, MFMA-sized steps)?  Its run is never the small form's.
@@ -424,12 +413,10 @@ inline bool sweep64_takes(const Plan& P, const DevSwitches& sw, SweepDesc* d) {
 // small-bond classifiers with a batch of a few dozen are such plans.  A small-bond sweep that is asked for and matches
 // takes the plan from the walker: the executor (and forms_check) then works on a copy whose steps are launches of their
 // own again, with the slot counts and collapse flags the planner gave them before it marked the plan.
-// The float64 form (CTN_SWEEP_SMALL64=1) does the same, where k_sweep_f64 would not take the un-chained plan.
+// On a float64 plan (CTN_SWEEP_SMALL64=1) only where k_sweep_f64 would not take the un-chained plan.
 inline bool sweep_small_unchains(const Plan& P, const DevSwitches& sw) {
-  if (!P.chain) return false;
-  SweepDesc d, d64, k64;
-  if (sweep_small_asked(P, sw) && sweep_small_match(P, &d)) return true;
-  return sweep_small_f64_asked(P, sw) && sweep_small_f64_match(P, &d64) && !sweep64_takes(P, sw, &k64);
+  SweepDesc d, k64;
+  return P.chain && sweep_small_asked(P, sw) && sweep_small_match(P, &d) && !sweep64_takes(P, sw, &k64);
 }
 inline Plan unchained(const Plan& P) {
   Plan Q = P;
@@ -785,19 +772,12 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.sweep_a = 2 * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * T;
       F.sweep = sd;
     } else if (SweepDesc ss; sweep_small_asked(P, sw) && sweep_small_match(P, &ss)) {
-      // small bonds (k_sweep_small_f32), only where neither form above took the plan: a record per (site, row block) and
-      // member entry - two per site of the two-step shape, one of the epilogue-summed shape
+      // small bonds (k_sweep_small, either type), only where neither form above took the plan: a record per (site, row
+      // block) and member entry - two per site of the two-step shape (float64: always), one of the epilogue-summed shape
       const size_t S = ss.two ? ss.steps.size() / 2 : ss.steps.size(), nrec = (size_t)R * S * ss.J;
       F.sweep_ids = ss.ids;
       F.sweep_a = (ss.two ? 2 : 1) * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * ss.steps.size();
       F.sweep = ss;
-    } else if (SweepDesc sf; sweep_small_f64_asked(P, sw) && sweep_small_f64_match(P, &sf)) {
-      // small bonds in float64 (k_sweep_small_f64, CTN_SWEEP_SMALL64=1), only where k_sweep_f64 did not take the plan: the
-      // records of the two-step shape above
-      const size_t S = sf.steps.size() / 2, nrec = (size_t)R * S * sf.J;
-      F.sweep_ids = sf.ids;
-      F.sweep_a = 2 * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * sf.steps.size();
-      F.sweep = sf;
     }
     for (int s : F.sweep.steps) {
       F.sweep_role[s] = s == F.sweep.steps.back() ? 2 : 1;

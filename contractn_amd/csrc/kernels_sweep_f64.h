@@ -254,8 +254,8 @@ __global__ __launch_bounds__(Sweep64Shape<D>::NT, 1) void k_sweep_f64(Sweep64Arg
 // terms are scaled by ldexp to the largest exponent among them (exact), summed in a fixed order, and the mean m 2^x
 // (1 <= m < 2) gives Z = log(m) + x ln 2: one log, one product, one sum - and exactly 0 for a mean of exactly 1.
 // -inf: an all-zero tensor; NaN: a non-finite record.  grid (2 S, R), 256 threads.
-// <TWO>: true - the float64 sweep and the two-step sites of k_sweep_small_f32, as described; false (the epilogue-summed sites
-// of k_sweep_small_f32, kernels_sweep_small.h) - ONE entry per site, E'_s: grid (S, R), rec_a [R][S][J], Z [R][S].
+// <TWO>: true - the float64 sweep and the two-step sites of k_sweep_small, as described; false (the epilogue-summed sites
+// of k_sweep_small<float>, kernels_sweep_small.h) - ONE entry per site, E'_s: grid (S, R), rec_a [R][S][J], Z [R][S].
 template <bool TWO>
 __global__ __launch_bounds__(256) void k_sweep64_z(const double* __restrict__ rec_a, const int32_t* __restrict__ rec_e, int S, int J,
                                                    double numelC, double numelE, double* __restrict__ Z) {
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void k_sweep64_z(const double* __restrict__ re
 }
 
 // k_sweep64_finish: the reference's rescale factors of the 2 S member steps from the Z_t, and the last site's rows at the
-// common scale.  grid (J, R), 256 threads.  <T, TWO>: the element type of the rows (double; float: k_sweep_small_f32, whose
+// common scale.  grid (J, R), 256 threads.  <T, TWO>: the element type of the rows (double; float: k_sweep_small<float>, whose
 // rows are D % 4 == 0 floats - the same 16-byte pieces) and, as in k_sweep64_z, whether a site has two entries or one.
 struct Sweep64Finish {
   void* const* ptrs;

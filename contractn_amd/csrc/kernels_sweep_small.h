@@ -1,54 +1,78 @@
-// kernels_sweep_small.h - the batched-MPS sweep of kernels_sweep.h at small bonds (8 ... 64): every site of the chain
-// inside ONE launch, ONE WAVE per block of 16 inputs, the state in registers from the first site to the last.
-// Part of the gfx950 contraction engine (see engine.hip).
+// kernels_sweep_small.h - the batched-MPS sweep of kernels_sweep.h at small bonds (8 ... 64), float32 and float64: every
+// site of the chain inside ONE launch, ONE WAVE per block of 16 inputs, the state in registers from the first site to the
+// last.  Part of the gfx950 contraction engine (see engine.hip).
 #pragma once
 #include "kernels_sweep_f64.h"
 
 namespace ctn {
 
 // ---------------------------------------------------------------------------
-// K-sweep-small-f32.  Per site, as in kernels_sweep.h,
+// K-sweep-small.  Per site, as in kernels_sweep.h,
 //
 //     C[b, (p, r)] = sum_l E[b, l] W_s[l, p, r]        E'[b, r] = sum_p x_s[b, p] C[b, (p, r)]
 //
 // for bonds D = 8 ... 64 (a multiple of 4), where the planner either keeps a site as TWO launched steps (a GEMM and the
-// streaming sum over p, both reporting a rescale factor: the shape of the float64 plan) or, from B D P >= 65536 on, as one
-// epilogue-summed step behind an absorbed marker.  <DB, P, TWO>: DB = ceil(D / 16) blocks of 16 values of l and of r,
-// the physical dimension, and which of the two plan shapes the records are for.  C exists in accumulators only.
+// streaming sum over p, both reporting a rescale factor: the one shape of a float64 plan - plan.cpp fuses the pair for
+// fp32 only) or, in float32 from B D P >= 65536 on, as one epilogue-summed step behind an absorbed marker.
+// <T, DB, P, TWO>: float (v_mfma_f32_16x16x4_f32) or double (v_mfma_f64_16x16x4_f64), DB = ceil(D / 16) blocks of 16
+// values of l and of r, the physical dimension, and which of the two plan shapes the records are for (double: TWO only).
+// C exists in accumulators only.
 //
-// v_mfma_f32_16x16x4_f32, D[i = r][j = b]:
-//   B operand: lane (j = b, kg = lane >> 4) holds E[b][l]; k-step t = 0..3 of a group G of 16 values of l pairs lane
-//              group kg with l = 16 G + 4 kg + t (the pairing of kernels_sweep.h);
-//   A operand: lane (i = lane & 15, kg) holds W_s[16 G + 4 kg + t][p][16 q + i] for the r-block q: 16 lanes read 64
-//              consecutive bytes;
-//   D: lane (b, g = lane >> 4) holds rows i = 4 g + e of r-block q in register e: r = 16 q + 4 g + e.
-// After the sum over p, register e of r-block q in lane (b, g) is E'[b][16 q + 4 g + e] - which is, under that pairing,
-// exactly the B operand of k-step t = e of group G = q of the NEXT site in lane (b, kg = g).  The state goes from
-// accumulator to operand with no LDS, no barrier and no lane movement, for the whole chain; a wave shares nothing with any
-// other wave, so a workgroup is ONE wave (a batch of 256 inputs spreads over 16 CUs, not 4) and the kernel has no LDS and
-// no barrier at all.
+// How the state gets from accumulator to operand.  Both instructions compute D[i = r][j = b] from
+//   A (16 x 4):  lane (i = lane & 15, kg = lane >> 4) holds A[i][k = kg] - ONE value per lane and k-step;
+//   B (4 x 16):  lane (j = lane & 15, kg = lane >> 4) holds B[k = kg][j];
+//   D (16 x 16): lane (j = lane & 15, h = lane >> 4) holds four rows i in registers e = 0 .. 3,
+// with j = b, the A operand W_s[l][p][16 q + i] of the r-block q and the B operand E[b][l].  A k-step contracts 4 values
+// of l, one per lane group kg; a group G of 16 values of l is four k-steps t.  After the sum over p, register e of
+// acc[.][q] in lane (b, h) is E' of that lane's row - and it is the B operand of k-step t = e of group G = q of the NEXT
+// site in lane (b, kg = h) exactly if that k-step gives lane group kg the value of l which is that row.  The two
+// instructions lay D out differently, so the pairing of (kg, t) with l differs:
+//                 D: register e of lane (b, h) is row    k-step t of group G pairs lane group kg with    16 lanes of a group read of W_s
+//   float32       i = 4 h + e                            l = 16 G + 4 kg + t  (as kernels_sweep.h)       64 consecutive bytes of row l
+//   float64       i = h + 4 e                            l = 16 G + 4 t + kg                             128 consecutive bytes of row l,
+//                 (kernels_sweep_f64.h: "lane (b, h = lane >> 4) holds row i = h + 4 e in register e", which is why its     the four groups four
+//                 columns are r = rb + 2 h + 8 e + c; kernels_zip_f64.h stores its E' rows by the same rule)                consecutive rows
+// (The float32 pairing used in float64 would contract E'[b][16 G + kg + 4 t] against W_s[16 G + 4 kg + t]: a transposition
+// of each group's 4 x 4 values of l.)  So the state goes from accumulator to operand with no LDS, no barrier and no lane
+// movement, for the whole chain; a wave shares nothing with any other wave, so a workgroup is ONE wave (a batch of 256
+// inputs spreads over 16 CUs, not 4) and the kernel has no LDS, no barrier and no atomics at all.
+// The first site's state: float32 E[b][16 G + 4 kg + 0 .. 3], one 16-byte load per group; float64 E[b][16 G + 4 e + kg],
+// four 8-byte loads per group with a stride of 4 doubles, not one wide load; the last site's stores are 16-byte and 8-byte
+// for the same reason.  Both happen once per chain.
 //
-// The A operand: direct 4-byte loads (a core is 1 ... 64 KiB and the same for every wave: L1 / L2 hits), requested 4 to 8
-// k-steps ahead into a register queue that runs on across site boundaries, as in k_sweep_f32.  This is the variant that
-// was measured (ahead of the per-site launches at all six shapes of tools/sweep_small_timing.py).  The
-// other candidate, a workgroup of several waves staging W_s in LDS behind one barrier per site, was NOT built and not
-// measured: it ties the waves of a workgroup together, where the point of this form is that a block of rows waits for nobody.
-// (A workgroup is one wave, not several, and W is zero-filled per element, not per float4: D % 4 == 0 would allow either.)
-// Ragged D: what a lane would read of W at or beyond D (l >= D or r >= D) is read from an in-bounds element instead and
-// cleared by an AND mask - per element and without a branch -, so the padded entries of C and of the state are exact zeros
-// on their own; the state's padded columns are never loaded from E and never stored.  Rows of a block past M: their state
-// and weights are zero, never stored.  Means use numel = 16 D.
+// The A operand: direct 4-byte / 8-byte loads (a core is 1 ... 64 KiB, float64 ... 128 KiB, and the same for every wave:
+// L1 / L2 hits), requested SSQ = 4 to 8 k-steps ahead into a register queue that runs on across site boundaries, as in
+// k_sweep_f32.  This is the variant that was measured (ahead of the per-site launches at all six shapes
+// of tools/sweep_small_timing.py).  The other candidate, a workgroup of several waves staging W_s in LDS behind one barrier
+// per site, was NOT built and not measured, in either type: it ties the waves of a workgroup together, where the point of
+// this form is that a block of rows waits for nobody.  (A workgroup is one wave, not several, and W is zero-filled per
+// element, not per float4: D % 4 == 0 would allow either.)
+// Ragged D: every request is unconditional and in bounds.  What a lane would read of W at or beyond D (l >= D or r >= D) is
+// read from an in-bounds element instead and cleared by an AND mask on the 32-bit / 64-bit value - per element and without
+// a branch -, so the padded entries of C and of the state are exact zeros on their own; the state's padded columns are
+// never loaded from E and never stored.  A lane whose column 16 (DB - 1) + i is at or beyond D reads column 0.  Rows of l:
+// in float32 a k-step of the last group is valid per lane (16 (DB - 1) + 4 kg + t < D), and a lane for which it is not
+// reads row 16 (DB - 1) + t; in float64 D is a multiple of 4, so it is valid or not for ALL four lane groups at once
+// (16 (DB - 1) + 4 t < D), and an invalid one reads the group's rows 16 (DB - 1) + kg instead.  Rows of a block past M:
+// their state and weights are zero, never stored.  Means use numel = 16 D.
 //
-// Stabilisation: k_sweep_f64's protocol (kernels_sweep_f64.h) in float.  A block rescales its rows by 2^e,
-// e = ilogb(mean |E'|), folded into the next site's weights x_s exactly; per (replica, site, block) the kernel records e,
-// the abs-sum of E' and - TWO - of C, both at the block's scale g[j][s - 1]; the abs-sums are sums over a lane's
-// registers in a fixed order, then over the lanes by six shuffle levels - spread over the NEXT site's k-steps, behind its
-// MFMAs: only that site's epilogue needs e -: no barrier, no atomics, the same bits every run.  k_sweep64_z<TWO> and
-// k_sweep64_finish<float, TWO> rebuild the reference's per-step rescale factors from the records.  !TWO: one entry per
-// site (the member step); the absorbed marker has no entry and reports 0.
+// Registers, float64 (a lone wave has 512: 256 VGPR + 256 AGPR, and MFMA accumulators may sit in AGPRs): state 8 DB,
+// accumulators 8 P DB, queue 2 SSQ P DB, plus 16-odd of offsets and masks: <4, 4> 32 + 128 + 128.  Float32 needs half of
+// each.  The compiler's remarks for all 24 instantiations are in DESIGN section 4: no scratch, no spills, the same queue
+// (sweep_small_queue) in both types and one pass over l.
 //
-// Conditions (fused_forms.h, sweep_small_match): fp32, 8 <= |l| = |r| <= 64 a multiple of 4, |p| = 2 or 4, W_s and x_s network
-// inputs with r and p unit-stride, E row-major, ldIn, ldOut, ldWl, ldWp multiples of 4 (16-byte accesses of the state's rows).
+// Stabilisation: k_sweep_f64's protocol (kernels_sweep_f64.h), in float or unchanged.  A block rescales its rows by 2^e,
+// e = ilogb(mean |E'|), folded into the next site's weights x_s exactly, |e| <= kSweepSmallMaxExp / kSweep64MaxExp; per
+// (replica, site, block) the kernel records e in rec_e and in rec_a the abs-sum of E' and - TWO - of C, both at the block's
+// scale g[j][s - 1]; the abs-sums are sums over a lane's registers in a fixed order (4 P DB values of C, 4 DB of E'), then
+// over the lanes by six shuffle levels - spread over the NEXT site's k-steps, behind its MFMAs: only that site's epilogue
+// needs e -: no barrier, no atomics, the same bits every run.  k_sweep64_z<TWO> and k_sweep64_finish<T, TWO> rebuild the
+// reference's per-step rescale factors from the records.  !TWO: one entry per site (the member step); the absorbed marker
+// has no entry and reports 0.
+//
+// Conditions (fused_forms.h, sweep_small_match): fp32 or fp64, 8 <= |l| = |r| <= 64 a multiple of 4, |p| = 2 or 4, W_s and
+// x_s network inputs with r and p unit-stride, E row-major, ldIn, ldOut, ldWl, ldWp multiples of 4 in float32 (16-byte
+// accesses of the state's rows), even in float64.
 // ---------------------------------------------------------------------------
 struct SweepSmallArgs {
   void* const* ptrs;         // [R][n_tensors]
@@ -73,9 +97,18 @@ template <int DB, int P>
 constexpr int sweep_small_queue() { return DB == 2 && P == 2 ? 8 : DB == 3 && P == 2 ? 6 : 4; }
 constexpr int kSweepSmallMaxExp = 100;   // |e| of one site at most: 2^-e stays a normal float
 
-template <int DB, int P, bool TWO>
-__global__ __launch_bounds__(64) void k_sweep_small_f32(SweepSmallArgs a) {
+// per element type: the bits of a value of W (the AND masks), a tile of accumulators, |e| of one site at most
+template <typename T> struct SweepSmallType;
+template <> struct SweepSmallType<float> { typedef uint32_t bits; typedef f32x4 acc; static constexpr int max_exp = kSweepSmallMaxExp; };
+template <> struct SweepSmallType<double> { typedef uint64_t bits; typedef f64x4 acc; static constexpr int max_exp = kSweep64MaxExp; };
+
+template <typename T, int DB, int P, bool TWO>
+__global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
   static_assert(DB >= 1 && DB <= 4 && (P == 2 || P == 4), "shape");
+  constexpr bool F32 = sizeof(T) == 4;
+  static_assert(F32 || TWO, "a float64 plan has two-step sites only");
+  typedef typename SweepSmallType<T>::bits bits_t;
+  constexpr int ES = sizeof(T);               // bytes per element
   constexpr int NK = 4 * DB;                  // k-steps per site
   constexpr int SSQ = sweep_small_queue<DB, P>();
   static_assert(NK % SSQ == 0 && SSQ <= NK, "queue");
@@ -87,8 +120,9 @@ __global__ __launch_bounds__(64) void k_sweep_small_f32(SweepSmallArgs a) {
   const int row = SWR * j + i16;              // this lane's input
   const bool row_ok = row < a.M;              // the last block of a batch that is not a multiple of 16: its other rows stay zero
 
-  // the chain's input, normalised by its producer's mean (the lazy rescale: reference einsum.py:387 on the step before)
-  float st[DB][4];
+  // the chain's input, normalised by its producer's mean (the lazy rescale: reference einsum.py:387 on the step before):
+  // register e of group G is E[b][16 G + 4 kg + e] (float32) or E[b][16 G + 4 e + kg] (float64)
+  T st[DB][4];
   {
     double pv = 0.0;
     if (a.partIn) {
@@ -100,57 +134,88 @@ __global__ __launch_bounds__(64) void k_sweep_small_f32(SweepSmallArgs a) {
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) pv += __shfl_xor(pv, o, 64);
     }
-    const float nI = (float)pv;
-    const float inv = (a.partIn && nI > (float)a.min_norm) ? 1.0f / (nI / (float)a.numelIn) : 1.0f;
-    const float* __restrict__ Ein = (const float*)tp[a.idIn] + (int64_t)row * a.ldIn;
+    const T nI = (T)pv;
+    const T inv = (a.partIn && nI > (T)a.min_norm) ? (T)1 / (nI / (T)a.numelIn) : (T)1;
+    const T* __restrict__ Ein = (const T*)tp[a.idIn] + (int64_t)row * a.ldIn;
 #pragma unroll
     for (int G = 0; G < DB; ++G) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row_ok && 16 * G + 4 * kg < D) v = *reinterpret_cast<const float4*>(Ein + 16 * G + 4 * kg);
-      st[G][0] = v.x * inv; st[G][1] = v.y * inv; st[G][2] = v.z * inv; st[G][3] = v.w * inv;
+      if constexpr (F32) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row_ok && 16 * G + 4 * kg < D) v = *reinterpret_cast<const float4*>(Ein + 16 * G + 4 * kg);
+        st[G][0] = v.x * inv; st[G][1] = v.y * inv; st[G][2] = v.z * inv; st[G][3] = v.w * inv;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          double v = 0.0;
+          if (row_ok && 16 * G + 4 * e < D) v = Ein[16 * G + 4 * e + kg];   // (D % 4 == 0: the four lane groups together)
+          st[G][e] = v * inv;
+        }
+      }
     }
   }
 
-  // a lane's own offsets into a core (bytes): its column of every (p, r-block) in row 0 of a group of l, and its own row
-  // 4 kg of the group.  k-step u = 4 G + t reads row 16 G + 4 kg + t.  Nothing of W at or beyond D is used, and every
-  // request is in bounds WITHOUT a branch (a conditional load makes the compiler wait for each request where it is made):
-  // only the last r-block can hold columns past D - such a lane reads column 0 - and only the last group rows past D -
-  // such a lane reads row 16 G + t, which is < D because D > 16 (DB - 1) is a multiple of 4 -, and what they read is
-  // cleared by an AND with an all-zero mask
+  // a lane's own offsets into a core (bytes): its column of every (p, r-block) in row 0 of a group of l, and its own row of
+  // the group - float32: row 4 kg, k-step u = 4 G + t reads row 16 G + 4 kg + t; float64: row kg of a k-step's four,
+  // k-step u = 4 G + e reads rows 16 G + 4 e + kg.  Nothing of W at or beyond D is used, and every request is in bounds
+  // WITHOUT a branch (a conditional load makes the compiler wait for each request where it is made): only the last r-block
+  // can hold columns past D - such a lane reads column 0 - and only the last group rows past D - such a lane reads row
+  // 16 G + t (float32), such a k-step rows 16 G + kg (float64), which are < D because D > 16 (DB - 1) is a multiple of 4 -,
+  // and what they read is cleared by an AND with an all-zero mask
   const bool c_ok = 16 * (DB - 1) + i16 < D;
-  uint32_t cmask = c_ok ? ~0u : 0u;
+  bits_t cmask = c_ok ? ~(bits_t)0 : (bits_t)0;
   uint32_t voff[P][DB];
 #pragma unroll
   for (int p = 0; p < P; ++p)
 #pragma unroll
-    for (int q = 0; q < DB; ++q) voff[p][q] = (uint32_t)(((int64_t)p * a.ldWp + (q < DB - 1 || c_ok ? 16 * q + i16 : 0)) * 4);
-  const uint32_t kgoff = (uint32_t)((int64_t)(4 * kg) * a.ldWl * 4);
-  uint32_t lmask[4], lko[4];                  // the last group's four k-steps
+    for (int q = 0; q < DB; ++q) {
+      if constexpr (F32) voff[p][q] = (uint32_t)(((int64_t)p * a.ldWp + (q < DB - 1 || c_ok ? 16 * q + i16 : 0)) * 4);
+      else voff[p][q] = (uint32_t)(((int64_t)p * a.ldWp + (q < DB - 1 || c_ok ? 16 * q + i16 : 0) + (int64_t)kg * a.ldWl) * 8);
+    }
+  bits_t lmask[4];                            // the last group's four k-steps (float64: the same in every lane)
+  uint32_t kgoff, lko[4];                     // float32: the lane's row 4 kg of a group, and of the last group's k-steps
+  int lrow[4];                                // float64: the first row of the last group's k-steps
+  if constexpr (F32) {
+    kgoff = (uint32_t)((int64_t)(4 * kg) * a.ldWl * 4);
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const bool l_ok = 16 * (DB - 1) + 4 * kg + t < D;
-    lmask[t] = l_ok ? ~0u : 0u;
-    lko[t] = l_ok ? kgoff : 0u;
-    asm volatile("" : "+v"(lmask[t]));        // (opaque: the masks stay masks, the loads unconditional)
+    for (int t = 0; t < 4; ++t) {
+      const bool l_ok = 16 * (DB - 1) + 4 * kg + t < D;
+      lmask[t] = l_ok ? ~0u : 0u;
+      lko[t] = l_ok ? kgoff : 0u;
+      asm volatile("" : "+v"(lmask[t]));      // (opaque: the masks stay masks, the loads unconditional)
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool l_ok = 16 * (DB - 1) + 4 * e < D;
+      lmask[e] = l_ok ? ~0ull : 0ull;
+      lrow[e] = l_ok ? 4 * e : 0;
+      asm volatile("" : "+v"(lmask[e]));
+    }
   }
   asm volatile("" : "+v"(cmask));
-  const int64_t stepW = a.ldWl * 4;           // next row of l (bytes)
+  const int64_t stepW = a.ldWl * ES;          // next row of l (bytes)
 
   sw_gptr Wcur = (sw_gptr)tp[a.site_ids[0]];
   sw_gptr Xcur = (sw_gptr)tp[a.site_ids[1]];
-  float wq[SSQ][P][DB];
-  auto wrequest = [&](float (&dst)[P][DB], sw_gptr core, int u) {     // k-step u of `core` (u a compile-time value)
+  T wq[SSQ][P][DB];
+  auto wrequest = [&](T (&dst)[P][DB], sw_gptr core, int u) {     // k-step u of `core` (u a compile-time value)
     const bool last_g = (u >> 2) == DB - 1;
-    const uint32_t ko = last_g ? lko[u & 3] : kgoff;
-    sw_gptr from = core + (int64_t)(16 * (u >> 2) + (u & 3)) * stepW;      // (wave-uniform)
+    uint32_t ko = 0;                          // (float64: the lane's row is in voff)
+    sw_gptr from;                             // (wave-uniform)
+    if constexpr (F32) {
+      ko = last_g ? lko[u & 3] : kgoff;
+      from = core + (int64_t)(16 * (u >> 2) + (u & 3)) * stepW;
+    } else {
+      from = core + (int64_t)(16 * (u >> 2) + (last_g ? lrow[u & 3] : 4 * (u & 3))) * stepW;
+    }
 #pragma unroll
     for (int p = 0; p < P; ++p)
 #pragma unroll
       for (int q = 0; q < DB; ++q) {
-        uint32_t v = *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(from + (voff[p][q] + ko));
+        bits_t v = *reinterpret_cast<const __attribute__((address_space(1))) bits_t*>(from + (voff[p][q] + ko));
         if (last_g) v &= lmask[u & 3];
         if (q == DB - 1) v &= cmask;
-        dst[p][q] = __uint_as_float(v);
+        dst[p][q] = __builtin_bit_cast(T, v);
       }
   };
 #pragma unroll
@@ -159,9 +224,10 @@ __global__ __launch_bounds__(64) void k_sweep_small_f32(SweepSmallArgs a) {
   // a block's record of site s: the abs-sums of C and E' (each lane's own share, then over the lanes by shuffles in a
   // fixed order) and the exponent it applies.  Only the NEXT site's epilogue needs the exponent, so the six shuffle levels of
   // site s are spread over the k-steps of site s + 1, behind its MFMAs; after the last site they are done at once.
-  auto record = [&](int s, double totC, double totE, float inv_before, bool last) {
+  auto record = [&](int s, double totC, double totE, T inv_before, bool last) {
+    constexpr int max_exp = SweepSmallType<T>::max_exp;
     int ex = 0;                               // an all-zero (or non-finite) block keeps its scale: the exponent stays finite
-    if (!last && totE > 0.0 && totE < INFINITY) ex = max(-kSweepSmallMaxExp, min(kSweepSmallMaxExp, ilogb(totE / (double)(SWR * D))));
+    if (!last && totE > 0.0 && totE < INFINITY) ex = max(-max_exp, min(max_exp, ilogb(totE / (double)(SWR * D))));
     if (lane == 0) {
       if (TWO) {
         const size_t ra = ((size_t)r * 2 * a.S + 2 * s) * a.J + j;
@@ -174,7 +240,7 @@ __global__ __launch_bounds__(64) void k_sweep_small_f32(SweepSmallArgs a) {
     }
     return ex;
   };
-  float inv_s = 1.0f;                         // 2^-e of the site before: the state in registers is the un-rescaled one
+  T inv_s = 1;                                // 2^-e of the site before: the state in registers is the un-rescaled one
   double pendC = 0.0, pendE = 0.0;            // the site before: this lane's share of its abs-sums, being summed over the lanes
   sw_gptr Wnext = Wcur, Xnext = Xcur;
   for (int s = 0; s < a.S; ++s) {
@@ -183,26 +249,28 @@ __global__ __launch_bounds__(64) void k_sweep_small_f32(SweepSmallArgs a) {
     const int sn = last ? s : s + 1;
     Wnext = (sw_gptr)tp[a.site_ids[2 * sn]];
     Xnext = (sw_gptr)tp[a.site_ids[2 * sn + 1]];
-    float xr[P];                               // the input's weights of this site
+    T xr[P];                                   // the input's weights of this site
     {
-      sw_gptr xp = Xcur + (int64_t)min(row, a.M - 1) * a.ldX * 4;
+      sw_gptr xp = Xcur + (int64_t)min(row, a.M - 1) * a.ldX * ES;
 #pragma unroll
-      for (int p = 0; p < P; ++p) xr[p] = *reinterpret_cast<const __attribute__((address_space(1))) float*>(xp + 4 * p);
+      for (int p = 0; p < P; ++p) xr[p] = *reinterpret_cast<const __attribute__((address_space(1))) T*>(xp + ES * p);
     }
-    f32x4 acc[P][DB];
+    typename SweepSmallType<T>::acc acc[P][DB];
 #pragma unroll
     for (int p = 0; p < P; ++p)
 #pragma unroll
       for (int q = 0; q < DB; ++q)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[p][q][e] = 0.f;
+        for (int e = 0; e < 4; ++e) acc[p][q][e] = 0;
 #pragma unroll
     for (int u = 0; u < NK; ++u) {
 #pragma unroll
       for (int p = 0; p < P; ++p)
 #pragma unroll
-        for (int q = 0; q < DB; ++q)
-          acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[u % SSQ][p][q], st[u >> 2][u & 3], acc[p][q], 0, 0, 0);
+        for (int q = 0; q < DB; ++q) {
+          if constexpr (F32) acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[u % SSQ][p][q], st[u >> 2][u & 3], acc[p][q], 0, 0, 0);
+          else acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(wq[u % SSQ][p][q], st[u >> 2][u & 3], acc[p][q], 0, 0, 0);
+        }
       if (u + SSQ < NK) wrequest(wq[u % SSQ], Wcur, u + SSQ);
       else wrequest(wq[u % SSQ], Wnext, u + SSQ - NK);
 #pragma unroll
@@ -214,33 +282,44 @@ __global__ __launch_bounds__(64) void k_sweep_small_f32(SweepSmallArgs a) {
     }
     if (s > 0) {
       const int ex = record(s - 1, pendC, pendE, inv_s, false);   // (inv_s: still the one site s - 1 worked with)
-      inv_s = ldexpf(1.0f, -ex);
+      inv_s = std::ldexp((T)1, -ex);
     }
-    // ---- the site's epilogue.  A lane has C[b = i16][p][16 q + 4 kg + e]: the complete sum over l.  The state is the
-    // un-rescaled one: its scale 2^-e goes into the weights (exact)
-    float xs[P];
+    // ---- the site's epilogue.  A lane has the complete sum over l of C[b = i16][p][16 q + 4 kg + e] (float32) or of
+    // C[b = i16][p][16 q + kg + 4 e] (float64).  The state is the un-rescaled one: its scale 2^-e goes into the weights (exact)
+    T xs[P];
 #pragma unroll
-    for (int p = 0; p < P; ++p) xs[p] = (row_ok ? xr[p] : 0.f) * inv_s;
-    float asumC = 0.f, asumE = 0.f;
+    for (int p = 0; p < P; ++p) xs[p] = (row_ok ? xr[p] : (T)0) * inv_s;
+    T asumC = 0, asumE = 0;
 #pragma unroll
     for (int q = 0; q < DB; ++q) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float v = xs[0] * acc[0][q][e];
-        float ac = fabsf(acc[0][q][e]);
+        T v = xs[0] * acc[0][q][e];
+        T ac = std::fabs(acc[0][q][e]);
 #pragma unroll
         for (int p = 1; p < P; ++p) {
-          v = fmaf(xs[p], acc[p][q][e], v);
-          ac += fabsf(acc[p][q][e]);
+          v = std::fma(xs[p], acc[p][q][e], v);
+          ac += std::fabs(acc[p][q][e]);
         }
         st[q][e] = v;
         if (TWO) asumC += ac;
-        asumE += fabsf(v);
+        asumE += std::fabs(v);
+        // the last site's rows leave with this block's own scale (k_sweep64_finish brings them to the common one)
+        if constexpr (!F32) {
+          if (last) {
+            if (row_ok && 16 * q + 4 * e < D) {
+              sw_gout64 og = (sw_gout64)tp[a.idOut] + (int64_t)row * a.ldOut + 16 * q + 4 * e + kg;
+              *og = v;
+            }
+          }
+        }
       }
-      if (last) {   // the last site's rows leave with this block's own scale (k_sweep64_finish brings them to the common one)
-        if (row_ok && 16 * q + 4 * kg < D) {
-          sw_gout og = (sw_gout)tp[a.idOut] + (int64_t)row * a.ldOut + 16 * q + 4 * kg;
-          *reinterpret_cast<__attribute__((address_space(1))) f32x4*>(og) = f32x4{st[q][0], st[q][1], st[q][2], st[q][3]};
+      if constexpr (F32) {
+        if (last) {
+          if (row_ok && 16 * q + 4 * kg < D) {
+            sw_gout og = (sw_gout)tp[a.idOut] + (int64_t)row * a.ldOut + 16 * q + 4 * kg;
+            *reinterpret_cast<__attribute__((address_space(1))) f32x4*>(og) = f32x4{st[q][0], st[q][1], st[q][2], st[q][3]};
+          }
         }
       }
     }

@@ -31,10 +31,10 @@ struct DevSwitches {
   int sweep = -1;        // CTN_SWEEP: 0 never walk a chain of epilogue-summed steps in one launch (k_sweep_f32), 1 whenever one matches (tests)
   int sweep64 = 1;       // CTN_SWEEP64=0: never the float64 sweep (k_sweep_f64), which CTN_SWEEP=1 takes on a float64 plan whose
                          // per-site step pairs (a GEMM and the streaming sum over p) match
-  int sweep_small = -1;  // CTN_SWEEP_SMALL: 1 a float32 batched MPS of bond 8 ... 64 is walked in one launch (k_sweep_small_f32) wherever
+  int sweep_small = -1;  // CTN_SWEEP_SMALL: 1 a float32 batched MPS of bond 8 ... 64 is walked in one launch (k_sweep_small<float>) wherever
                          // sweep_small_match takes it, k_sweep_f32 does not and CTN_SWEEP is not 0; 0 or unset: never (kSweepSmallDefault)
-  int sweep_small64 = -1;  // CTN_SWEEP_SMALL64: 1 a float64 batched MPS of bond 8 ... 64 is walked in one launch (k_sweep_small_f64)
-                         // wherever sweep_small_f64_match takes it, k_sweep_f64 does not and neither CTN_SWEEP nor CTN_SWEEP64 is 0;
+  int sweep_small64 = -1;  // CTN_SWEEP_SMALL64: 1 a float64 batched MPS of bond 8 ... 64 is walked in one launch (k_sweep_small<double>)
+                         // wherever sweep_small_match takes it, k_sweep_f64 does not and neither CTN_SWEEP nor CTN_SWEEP64 is 0;
                          // 0 or unset: never (kSweepSmallF64Default).  CTN_SWEEP_SMALL does not reach a float64 plan, nor this a float32 one
   int dot_tr = 1;        // CTN_DOT_TR=0: full dots against a transposed tensor stay on k_dot_split's 4-byte gathers
   int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches

@@ -191,7 +191,7 @@ void ctn_exec_destroy(ctn_exec* exec);
  *                  such a chain as TWO steps - the GEMM `bl,plr->bpr` and the streaming sum `bpr,bp->br` - and when
  *                  k_sweep_f64 walks it (CTN_SWEEP=1) BOTH are members: two entries per site, each the reference's own
  *                  factor of that step (tile (1, 1) for all but the last member, (16, D P) for the last), reconstructed
- *                  from the row blocks' abs-sums of C and of E' and their power-of-two scales.  k_sweep_small_f64
+ *                  from the row blocks' abs-sums of C and of E' and their power-of-two scales.  k_sweep_small<double>
  *                  (CTN_SWEEP_SMALL64=1, bonds 8 ... 64) reports in the same way: both member steps of a site report
  *                  their factor.
  */
@@ -295,7 +295,7 @@ int ctn_exec_merge_scales(ctn_exec* exec, int t_dtype, void* buf, int64_t stride
  * many full long-K tiles -> 256 x 256.  Measurement tooling only (bench.py keys its per-kernel roofline on it).
  * A step that runs inside the launch of a later one (see step_rescales above) reports (1, 1); the fused forms report
  * tiles no plain form has: the zipper pairs (512, 256), (512, 128), (512, 64), (256, 32), (512, 512), (32, 256), (64, 256 with
- * (1, 1) before it); a sweep (16, D P) - k_sweep_small_f32 and k_sweep_small_f64 at the last member step, (1, 1) at the others -; the complex pair k_cmfma_f32 (64, 256) behind the (1, 1) of its S step.
+ * (1, 1) before it); a sweep (16, D P) - k_sweep_small<float> and <double> at the last member step, (1, 1) at the others -; the complex pair k_cmfma_f32 (64, 256) behind the (1, 1) of its S step.
  * The fp64 latency form k_zip_lat_f64 reports (32, 256) behind the (1, 1) of its absorbed step, exactly as k_zip_lat does.
  */
 int ctn_exec_step_tile(const ctn_exec* exec, int step, int32_t* tile_m, int32_t* tile_n);
@@ -318,9 +318,9 @@ typedef enum {
   CTN_FORM_ZIPQP = 7,   /* k_zipqp_f32: k_zipq_f32 with a workgroup that walks several work items of the launch */
   CTN_FORM_ZIPL_F64 = 8, /* k_zip_lat_f64: the float64 latency form, tile (32, 256) (the fp32 latency form k_zip_lat reports NONE) */
   CTN_FORM_ZIP512 = 9,  /* k_zip512_f32: the bond-512 pair on 16 x 16 x 4 MFMAs, 64 values of u per workgroup, tile (512, 512) */
-  CTN_FORM_SWEEP_SMALL = 10, /* k_sweep_small_f32: a batched MPS of bond 8 ... 64 in one launch, at its last member step, tile (16, D P) -
+  CTN_FORM_SWEEP_SMALL = 10, /* k_sweep_small<float> ("k_sweep_small_f32"): a batched MPS of bond 8 ... 64 in one launch, at its last member step, tile (16, D P) -
                                 with the next one the forms here that are no zipper pair (k_sweep_f32 and k_sweep_f64 report NONE) */
-  CTN_FORM_SWEEP_SMALL_F64 = 11 /* k_sweep_small_f64: the same in float64 (CTN_SWEEP_SMALL64=1), at its last member step, tile (16, D P) */
+  CTN_FORM_SWEEP_SMALL_F64 = 11 /* k_sweep_small<double> ("k_sweep_small_f64"): the same in float64 (CTN_SWEEP_SMALL64=1), at its last member step, tile (16, D P) */
 } ctn_step_form;
 int ctn_exec_step_form(const ctn_exec* exec, int step, int32_t* form);
 

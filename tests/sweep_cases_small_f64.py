@@ -1,5 +1,5 @@
 """Open batched-MPS networks of SMALL bond (8 ... 64) in float64 for the element-wise checks of k_sweep_small_f64
-(contractn_amd/csrc/kernels_sweep_small_f64.h, CTN_SWEEP_SMALL64=1) and its bookkeeping (k_sweep64_z<true>,
+(k_sweep_small<double> of contractn_amd/csrc/kernels_sweep_small.h, CTN_SWEEP_SMALL64=1) and its bookkeeping (k_sweep64_z<true>,
 k_sweep64_finish<double, true>): the cases, the bounds with their derivation, the checks themselves and a NumPy model of
 the kernel's arithmetic.  Shared by tests/test_gpu_sweep_small_f64.py (GPU) and tests/test_sweep_small_f64_cases_host.py,
 tests/test_sweep_small_f64_forms_host.py (no GPU).  The networks are sweep_cases.Net, the operands its perm_operands and
@@ -9,7 +9,7 @@ rescales_ld there); nothing here touches the engine.
 The float64 plan keeps EVERY site as two launched steps, (E . W_s) -> bpr and (. x_s) -> br: all 2 S are members of the
 sweep and both report a rescale factor.
 
-What the kernel's text gives (kernels_sweep_small_f64.h): ONE wave owns 16 inputs and the whole range of l and of r.  Its
+What the kernel's text gives (kernels_sweep_small.h, T = double): ONE wave owns 16 inputs and the whole range of l and of r.  Its
 paths are the eight <DB = ceil(D / 16), P> instantiations, a full and a ragged D (the masked k-steps and columns of W), a
 full and a ragged last block of rows (B = 40: 16 + 16 + 8; 17: 16 + 1; 1), the first / middle / last site, the load queue
 that runs across site boundaries (one site is 4 DB k-steps: at DB = 1 the whole queue is always the next site's), a produced
