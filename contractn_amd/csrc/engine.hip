@@ -526,7 +526,7 @@ static int launch_sweep64(Exec* E, int s) {
 }
 
 // the last member of a small-bond sweep (float: CTN_SWEEP_SMALL=1, double: CTN_SWEEP_SMALL64=1): S sites of two member
-// steps each (`two`; double always) or of one
+// steps each (`two`; double always) or of one; `tr`: the cores are stored with the contracted bond unit-stride
 template <typename T, bool TWO>
 static int launch_sweep_small(Exec* E, int s) {
   const Plan& P = *E->plan;
@@ -547,7 +547,10 @@ static int launch_sweep_small(Exec* E, int s) {
     const int DB = (sd.D + 15) / 16;
 #define CTN_SWEEP_SMALL_LAUNCH(BB)                                                                          \
     do {                                                                                                    \
-      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small<T, BB, 4, TWO>), gs, dim3(64), 0, E->stream, w);    \
+      if (sd.tr) {                                                                                          \
+        if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small<T, BB, 4, TWO, true>), gs, dim3(64), 0, E->stream, w);  \
+        else hipLaunchKernelGGL((k_sweep_small<T, BB, 2, TWO, true>), gs, dim3(64), 0, E->stream, w);       \
+      } else if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small<T, BB, 4, TWO>), gs, dim3(64), 0, E->stream, w);   \
       else hipLaunchKernelGGL((k_sweep_small<T, BB, 2, TWO>), gs, dim3(64), 0, E->stream, w);               \
     } while (0)
     if (DB == 1) CTN_SWEEP_SMALL_LAUNCH(1);

@@ -5,7 +5,7 @@
 //
 // Every argument is one setting: the networks in flight (R, default 1), the chip's CUs (CU, default 256) and development
 // switches by the names of their environment variables without the CTN_ prefix (ZIP, ZIPQ, ZIPL, ZIPL_MP, ZIPL_MAX_R, ZIPL64,
-// ZIP128, ZIPM64, ZIP512, CPLX, SWEEP, SWEEP64, SWEEP_SMALL, SWEEP_SMALL64, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
+// ZIP128, ZIPM64, ZIP512, CPLX, SWEEP, SWEEP64, SWEEP_SMALL, SWEEP_SMALL64, SWEEP_SMALL_TR, GROUP, ARES, ARES_NTW, DOT_TR) - filled into a DevSwitches directly, the
 // environment is not read.  ALIAS_LD=<n> is no switch but a change to the PLAN, for the one rule of the sweep matchers that
 // no planner-made layout reaches: the result of the run that sweep_small_match finds is moved onto the run's input in the
 // workspace, with rows n elements apart (a two-step run; n = the input's own row stride must stay taken, any other refused).
@@ -18,7 +18,7 @@
 //     forms=[<step>:<ctn_step_form>/zu<zu>/zm<zm>,..] lat=[<step>:mp<mp>/prev<0|1>/next<0|1>/buf<0|1>,..] cplx=[<sp>+<step>,..]
 //     partials=<n per step,..> off=<per step,..> slots=<n> scratch=<n>
 //     bufs=slab:<n>,fold:<n>,zl:<n>,group:<n>,sweep:<a>/<s>/<z>/<l>/<e>,tabs:<n>
-//     sweep=[<member steps,..>]<f32|f64|small2|small1|small2f64|-> ares=[<step>:<ntw>,..] dot=[<step>,..] groups=[<head>:<len>,..]
+//     sweep=[<member steps,..>]<f32|f64|small2|small1|small2f64|->[/tr: a small run of transposed cores] ares=[<step>:<ntw>,..] dot=[<step>,..] groups=[<head>:<len>,..]
 //     side=[<tensor>:<buffer>,..]x<bytes>x<buffers> ok | <the invariant that failed>
 //
 // and these invariants are checked on each: a step's descriptor is on exactly under its role; an absorbed step is
@@ -65,6 +65,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     else if (key == "SWEEP64") d.sweep64 = v;
     else if (key == "SWEEP_SMALL") d.sweep_small = v;
     else if (key == "SWEEP_SMALL64") d.sweep_small64 = v;
+    else if (key == "SWEEP_SMALL_TR") d.sweep_small_tr = v;
     else if (key == "GROUP") d.group = v;
     else if (key == "ARES") d.ares = v;
     else if (key == "ARES_NTW") d.ares_ntw = v;
@@ -155,7 +156,7 @@ static void print_line(int plan, int set, const Plan& P, const FusedForms& F) {
          "side=[%s]x%lldx%d %s\n",
          plan, set, roles.c_str(), forms.c_str(), lat.c_str(), cplx.c_str(), partials.c_str(), offs.c_str(), (long long)F.part_slots,
          (long long)F.scratch_need, F.slab_elems, F.fold_elems, (long long)F.zl_slab_elems, F.group_args, F.sweep_a, F.sweep_s,
-         F.sweep_z, F.sweep_l, F.sweep_e, F.cplx_tabs.size(), sweep.c_str(), !F.sweep.on ? "-" : F.sweep.small ? (F.sweep.f64 ? "small2f64" : F.sweep.two ? "small2" : "small1") : F.sweep.f64 ? "f64" : "f32",
+         F.sweep_z, F.sweep_l, F.sweep_e, F.cplx_tabs.size(), sweep.c_str(), F.sweep.on && F.sweep.tr ? (F.sweep.f64 ? "small2f64/tr" : F.sweep.two ? "small2/tr" : "small1/tr") : !F.sweep.on ? "-" : F.sweep.small ? (F.sweep.f64 ? "small2f64" : F.sweep.two ? "small2" : "small1") : F.sweep.f64 ? "f64" : "f32",
          ares.c_str(), dot.c_str(), groups.c_str(), side.c_str(), (long long)F.zqp_side_bytes, F.zqp_side_bufs,
          invariants(P, F).c_str());
 }
@@ -203,7 +204,7 @@ int main(int argc, char** argv) {
       // (a small-bond sweep that is asked for takes a chain plan from the chain walker: the executor's own first decision)
       Plan Q = sweep_small_unchains(P, sets[j].sw) ? unchained(P) : P;
       SweepDesc sd;
-      const bool found = sweep_small_match(Q, &sd);
+      const bool found = sweep_small_match(Q, &sd, sets[j].sw.sweep_small_tr != 0);
       if (sets[j].w_ldl > 0 && found && sd.f64)
         for (size_t i = 0; i < sd.ids.size(); i += 2) {
           Tensor& core = Q.tensors[sd.ids[i]];

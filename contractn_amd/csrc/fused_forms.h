@@ -61,7 +61,10 @@ struct SweepDesc {
   // small bonds (kernels_sweep_small.h): `two` - the members are the 2 S steps of S two-step sites, as in float64; else
   // the S epilogue-summed steps (float32 only).  ids and idIn are filled in both shapes.  small && f64: k_sweep_small<double>,
   // always `two`.
-  bool small = false, two = false;
+  // tr (small only): every core of the run is stored TRANSPOSED - the bond contracted with the state is its unit-stride
+  // axis and the bond it keeps has the stride ldWl (k_sweep_small<.., TR = true>); else the kept bond is unit-stride and
+  // ldWl is the contracted one's.  ldWl is the stride of the core's non-unit bond either way.
+  bool small = false, two = false, tr = false;
 };
 // A full dot of a tensor with a transposed one (k_dot_tr), found on the plan's tables
 struct DotTr { bool on = false; int Ka = 0, Kb = 0, x_is_a = 1; int64_t ldY = 0; };
@@ -164,7 +167,7 @@ static constexpr bool kCplxDefault = false;
 // Is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
 // offset tables: E row-major [b][l], W[l][p][r] with r unit-stride, x[b][p] with p unit-stride, result rows [b][r].
 // `small`: as one site of k_sweep_small<float> instead - any bond 8 ... 64 that is a multiple of 4, x rows of any stride >= |p|.
-struct SweepShape { int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
+struct SweepShape { int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; bool tr = false; };
 inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh, bool small = false) {
   const Step& st = P.steps[s];
   const int D = (int)st.K, Pd = st.epw;
@@ -180,23 +183,45 @@ inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh, bool small = 
   const int32_t *omA = T + st.t.omA, *okA = T + st.t.okA, *onB = T + st.t.onB, *okB = T + st.t.okB, *omC = T + st.t.omC,
                 *onC = T + st.t.onC, *omX = T + st.t.omA2;
   const int64_t M = st.M;
-  const int64_t ldA = M > 1 ? omA[1] : D, ldC = M > 1 ? omC[1] : D, ldX = M > 1 ? omX[1] : Pd, ldWl = okB[1];
+  const int64_t ldA = M > 1 ? omA[1] : D, ldC = M > 1 ? omC[1] : D, ldX = M > 1 ? omX[1] : Pd;
+  // `small` alone: a TRANSPOSED core W[r][p][l] - l, the bond contracted with E, unit-stride and r at the stride ldWl
+  const bool tr = small && okB[1] == 1;
+  int64_t ldWl = okB[1];
   for (int64_t m = 0; m < M; ++m)
     if (omA[m] != m * ldA || omC[m] != m * ldC || omX[m] != m * ldX) return false;
   for (int k = 0; k < D; ++k)
-    if (okA[k] != k || okB[k] != (int64_t)k * ldWl) return false;
+    if (okA[k] != k || okB[k] != (int64_t)k * okB[1]) return false;
   int64_t ldWp = INT64_MAX;
-  for (int n = 0; n < D * Pd; ++n)
-    if (onB[n] >= D) ldWp = std::min<int64_t>(ldWp, onB[n]);
-  if (ldWp == INT64_MAX) return false;
   std::vector<char> seen((size_t)D * Pd, 0);
-  for (int n = 0; n < D * Pd; ++n) {
-    const int64_t off = onB[n], pp = off / ldWp, rr = off % ldWp;
-    if (off < 0 || pp >= Pd || rr >= D || onC[n] != rr || seen[(size_t)(pp * D + rr)]) return false;
-    seen[(size_t)(pp * D + rr)] = 1;
+  if (tr) {
+    // column n of C is (pp, rr) with rr = onC[n] its place in a row of E': onB[n] = pp ldWp + rr ldWl, so the stride of r
+    // is the offset of (0, 1) and that of p the smallest nonzero offset of a column with rr = 0
+    ldWl = INT64_MAX;
+    for (int n = 0; n < D * Pd; ++n) {
+      if (onC[n] == 1) ldWl = std::min<int64_t>(ldWl, onB[n]);
+      if (onC[n] == 0 && onB[n] > 0) ldWp = std::min<int64_t>(ldWp, onB[n]);
+    }
+    if (ldWl == INT64_MAX || ldWp == INT64_MAX || ldWl <= 0) return false;
+    for (int n = 0; n < D * Pd; ++n) {
+      const int64_t rr = onC[n], rest = rr >= 0 && rr < D ? onB[n] - rr * ldWl : -1, pp = rest / ldWp;
+      if (rest < 0 || rest % ldWp || pp >= Pd || seen[(size_t)(pp * D + rr)]) return false;
+      seen[(size_t)(pp * D + rr)] = 1;
+    }
+  } else {
+    for (int n = 0; n < D * Pd; ++n)
+      if (onB[n] >= D) ldWp = std::min<int64_t>(ldWp, onB[n]);
+    if (ldWp == INT64_MAX) return false;
+    for (int n = 0; n < D * Pd; ++n) {
+      const int64_t off = onB[n], pp = off / ldWp, rr = off % ldWp;
+      if (off < 0 || pp >= Pd || rr >= D || onC[n] != rr || seen[(size_t)(pp * D + rr)]) return false;
+      seen[(size_t)(pp * D + rr)] = 1;
+    }
   }
   if (ldA < D || ldC < D || ldA % 4 || ldC % 4 || (!small && ldX % Pd) || ldX < Pd || ldWl % 4 || ldWp % 4 || ldWl < D) return false;
-  if (((D + 12) * ldWl + 3 * ldWp + D) * 4 >= ((int64_t)1 << 31)) return false;   // a lane's offsets into a core: 32 bits
+  // a lane's offsets into a core: 32 bits.  (Transposed: the largest is row D - 1 of r, p = 3 and the lane's four values
+  // of l, ((D - 1) ldWl + 3 ldWp + 12) 4 bytes - below the same bound, which is kept for both.)
+  if (((D + 12) * ldWl + 3 * ldWp + D) * 4 >= ((int64_t)1 << 31)) return false;
+  sh->tr = tr;
   sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = D; sh->Pd = Pd;
   return true;
 }
@@ -222,7 +247,8 @@ inline bool sweep_match(const Plan& P, SweepDesc* d, bool small = false) {
         break;
       // the consumer of the run's last result: a member if it has the same shape and takes it as its E
       if (P.steps[s].lhs == P.steps[run.back()].out && sweep_step_shape(P, s, &cur, small) && cur.M == first.M && cur.D == first.D &&
-          cur.Pd == first.Pd && cur.ldWl == first.ldWl && cur.ldWp == first.ldWp && cur.ldX == first.ldX && cur.ldA == last.ldC) {
+          cur.Pd == first.Pd && cur.ldWl == first.ldWl && cur.ldWp == first.ldWp && cur.ldX == first.ldX && cur.ldA == last.ldC &&
+          cur.tr == first.tr) {                    // (a core stored the other way round ends the run)
         run.push_back(s);
         last = cur;
         continue;
@@ -247,7 +273,7 @@ inline bool sweep_match(const Plan& P, SweepDesc* d, bool small = false) {
       if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
     }
   }
-  d->on = true; d->steps = best; d->small = small;
+  d->on = true; d->steps = best; d->small = small; d->tr = best_first.tr;
   if (small) {
     d->idIn = P.steps[best.front()].lhs;
     for (int s : best) { d->ids.push_back(P.steps[s].rhs); d->ids.push_back(P.steps[s].lhs2); }
@@ -276,7 +302,7 @@ static constexpr bool kSweepF64Default = false;
 // input may be the very region its result lands on, with the same row stride (the aliasing rule below) - one parity for
 // both; ldWl and ldWp so that each 128-byte run that the 16 lanes of a group read of a core starts 16-byte aligned, as
 // k_sweep_f64's own condition has it (a bond-64 plan is refused by both kernels or by neither on its strides).
-struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; };
+struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; bool tr = false; };
 inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, bool small = false) {
   if ((P.dtype != CTN_F64 && !(small && P.dtype == CTN_F32)) || sb + 1 >= P.n_steps) return false;   // a step must follow the last member
   const Step& a = P.steps[sa];
@@ -310,14 +336,19 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, b
   const bool bond_ok = small ? (D >= 8 && D <= 64 && D % 4 == 0) : (D == 64 || D == 128 || D == 256 || D == 512);
   if (!bond_ok || (Pd != 2 && Pd != 4) || tW.dims[axis(tW, lr)] != D || M >= ((int64_t)1 << 31) - kFormSWR)
     return false;
-  if (tE.strides[el] != 1 || tW.strides[axis(tW, lr)] != 1 || tX.strides[axis(tX, lp)] != 1 || tO.strides[axis(tO, lr)] != 1) return false;
+  // `small`: exactly one of the core's two bonds is unit-stride - r, or (tr: a transposed core) l; ldWl is the other's stride
+  const bool tr = small && tW.strides[axis(tW, ll)] == 1 && tW.strides[axis(tW, lr)] != 1;
+  if (tE.strides[el] != 1 || tW.strides[axis(tW, tr ? ll : lr)] != 1 || tX.strides[axis(tX, lp)] != 1 || tO.strides[axis(tO, lr)] != 1) return false;
   const int64_t ldA = tE.strides[1 - el], ldC = tO.strides[axis(tO, lb)], ldX = tX.strides[axis(tX, lb)];
-  const int64_t ldWl = tW.strides[axis(tW, ll)], ldWp = tW.strides[axis(tW, lp)];
+  const int64_t ldWl = tW.strides[axis(tW, tr ? lr : ll)], ldWp = tW.strides[axis(tW, lp)];
   if (ldA < D || ldC < D || ldX < Pd || ldWl <= 0 || ldWp <= 0) return false;
   if (small ? ((ldA | ldC | ldWl | ldWp) & (P.dtype == CTN_F64 ? 1 : 3)) != 0 : ((ldA | ldC | ldX | ldWl | ldWp) & 1) != 0) return false;
   // a lane's offsets into a core: 32 bits, in bytes.  (8-byte elements: the largest a lane of k_sweep_small<double> forms is
-  // (3 ldWl + 3 ldWp + D) 8 < 2^28 x 8 = 2^31; the rows 16 G + 4 e go into the 64-bit base.)
+  // (3 ldWl + 3 ldWp + D) 8 < 2^28 x 8 = 2^31; the rows 16 G + 4 e go into the 64-bit base.  Transposed: row D - 1 of r,
+  // p = 3 and the lane's place in a group, ((D - 1) ldWl + 3 ldWp + 12) 4 or ((D - 1) ldWl + 3 ldWp + 3) 8 bytes - both
+  // below the same bound.)
   if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;
+  sh->tr = tr;
   sh->idE = idE; sh->idW = idW; sh->idX = idX; sh->idOut = b.out;
   sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = (int)D; sh->Pd = (int)Pd;
   return true;
@@ -343,7 +374,8 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
       const int na = next_launched(run.back());
       const int nb = na < P.n_steps ? next_launched(na) : na;
       if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur, small) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
-          cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC)
+          cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC ||
+          cur.tr != first.tr)                      // (a core stored the other way round ends the run)
         break;
       run.push_back(na); run.push_back(nb);
       ids.push_back(cur.idW); ids.push_back(cur.idX);
@@ -364,7 +396,7 @@ inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
       if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
     }
   }
-  d->on = true; d->f64 = P.dtype == CTN_F64; d->small = small; d->two = true; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
+  d->on = true; d->f64 = P.dtype == CTN_F64; d->small = small; d->two = true; d->tr = best_first.tr; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
   d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
   d->J = (int)((best_first.M + kFormSWR - 1) / kFormSWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
   return true;
@@ -385,10 +417,11 @@ static constexpr bool kSweepSmallF64Default = false;
 // whichever walks more sites.  Float64: the longest run of two-step sites - the one shape a float64 plan has.  Both
 // matchers keep their two safety rules: nothing launched between members, and the run's result overlaps its input only
 // as the same region with the same row stride.  At most kFormSweepMaxSites sites.
-inline bool sweep_small_match(const Plan& P, SweepDesc* d) {
+// `tr_ok` false (CTN_SWEEP_SMALL_TR=0): a run of transposed cores is not taken.
+inline bool sweep_small_match(const Plan& P, SweepDesc* d, bool tr_ok = true) {
   if (P.dtype != CTN_F32 && P.dtype != CTN_F64) return false;
   SweepDesc two, one;
-  const bool m2 = sweep64_match(P, &two, true), m1 = P.dtype == CTN_F32 && sweep_match(P, &one, true);
+  const bool m2 = sweep64_match(P, &two, true) && (tr_ok || !two.tr), m1 = P.dtype == CTN_F32 && sweep_match(P, &one, true) && (tr_ok || !one.tr);
   if (!m1 && !m2) return false;
   *d = (m2 && (!m1 || two.steps.size() / 2 >= one.steps.size())) ? two : one;
   return (int)(d->two ? d->steps.size() / 2 : d->steps.size()) <= kFormSweepMaxSites;
@@ -416,7 +449,7 @@ inline bool sweep64_takes(const Plan& P, const DevSwitches& sw, SweepDesc* d) {
 // On a float64 plan (CTN_SWEEP_SMALL64=1) only where k_sweep_f64 would not take the un-chained plan.
 inline bool sweep_small_unchains(const Plan& P, const DevSwitches& sw) {
   SweepDesc d, k64;
-  return P.chain && sweep_small_asked(P, sw) && sweep_small_match(P, &d) && !sweep64_takes(P, sw, &k64);
+  return P.chain && sweep_small_asked(P, sw) && sweep_small_match(P, &d, sw.sweep_small_tr != 0) && !sweep64_takes(P, sw, &k64);
 }
 inline Plan unchained(const Plan& P) {
   Plan Q = P;
@@ -771,7 +804,7 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.sweep_ids = sd.ids;
       F.sweep_a = 2 * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * T;
       F.sweep = sd;
-    } else if (SweepDesc ss; sweep_small_asked(P, sw) && sweep_small_match(P, &ss)) {
+    } else if (SweepDesc ss; sweep_small_asked(P, sw) && sweep_small_match(P, &ss, sw.sweep_small_tr != 0)) {
       // small bonds (k_sweep_small, either type), only where neither form above took the plan: a record per (site, row
       // block) and member entry - two per site of the two-step shape (float64: always), one of the epilogue-summed shape
       const size_t S = ss.two ? ss.steps.size() / 2 : ss.steps.size(), nrec = (size_t)R * S * ss.J;

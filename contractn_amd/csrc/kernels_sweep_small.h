@@ -56,6 +56,23 @@ namespace ctn {
 // (16 (DB - 1) + 4 t < D), and an invalid one reads the group's rows 16 (DB - 1) + kg instead.  Rows of a block past M:
 // their state and weights are zero, never stored.  Means use numel = 16 D.
 //
+// Transposed cores, <.., TR = true>.  The same MPS walked from its other end (the boundary vector on the right, cores stored
+// (r, p, l) or (p, r, l)): the bond a core contracts with the state is its unit-stride axis, W_s[r][p][l] with r at the stride
+// ldWl.  TR = false is the text described above, instruction for instruction; TR = true changes only how the A operand is
+// fetched - lane (i, kg) needs W_s[16 q + i][p][l] with l from the pairing:
+//   float32   l = 16 G + 4 kg + t, t = 0 .. 3 consecutive in memory: ONE 16-byte request per (G, p, q) delivers all four k-steps
+//             of a group, so the queue holds whole groups (sweep_small_queue_tr) and the site's loop runs a group at a time,
+//             (p, q) by (p, q) - the four MFMAs of an entry free it, and it is requested again at once for SG groups on;
+//   float64   l = 16 G + 4 t + kg: 8-byte requests, one per k-step, the four lane groups reading 32 consecutive bytes of a
+//             row; queue and loop are the forward ones, only the lane's offsets and the step between k-steps differ.
+// Ragged D as above: a row 16 (DB - 1) + i >= D of r reads row 0; in float32 a lane's four l of the last group are valid or
+// not as a whole (D % 4 == 0) and an invalid lane reads the group's first four; in float64 a k-step is valid or not for all
+// lanes and an invalid one reads l = 16 (DB - 1) + kg; all cleared by the AND masks.  Every accumulator meets the same
+// operand values in the same order u = 0 .. 4 DB - 1 as the forward kernel on the cores stored the other way round, and from
+// the MFMAs on nothing differs: the same bits (rec_a, rec_e, every factor).  The 16-byte requests rest on what the 16-byte
+// loads of a network-input E rest on: the engine refuses operand pointers that are not 16-byte aligned, and ldWl, ldWp are
+// multiples of 4.  Remarks and measurement: DESIGN sections 4, 10 and 11 (3d).
+//
 // Registers, float64 (a lone wave has 512: 256 VGPR + 256 AGPR, and MFMA accumulators may sit in AGPRs): state 8 DB,
 // accumulators 8 P DB, queue 2 SSQ P DB, plus 16-odd of offsets and masks: <4, 4> 32 + 128 + 128.  Float32 needs half of
 // each.  The compiler's remarks for all 24 instantiations are in DESIGN section 4: no scratch, no spills, the same queue
@@ -71,7 +88,7 @@ namespace ctn {
 // has no entry and reports 0.
 //
 // Conditions (fused_forms.h, sweep_small_match): fp32 or fp64, 8 <= |l| = |r| <= 64 a multiple of 4, |p| = 2 or 4, W_s and
-// x_s network inputs with r and p unit-stride, E row-major, ldIn, ldOut, ldWl, ldWp multiples of 4 in float32 (16-byte
+// x_s network inputs with r (TR: l) and p unit-stride, E row-major, ldIn, ldOut, ldWl, ldWp multiples of 4 in float32 (16-byte
 // accesses of the state's rows), even in float64.
 // ---------------------------------------------------------------------------
 struct SweepSmallArgs {
@@ -81,7 +98,7 @@ struct SweepSmallArgs {
   int32_t idIn, idOut;       // the chain's input E [b][l] and its output E' [b][r]
   int32_t S, J, M, D;        // sites, row blocks (ceil(rows / 16)), rows, bond dimension
   int64_t ldIn, ldOut;       // row strides of input and output (elements)
-  int64_t ldWl, ldWp;        // W_s[l][p][r]: strides of l and p (r unit-stride)
+  int64_t ldWl, ldWp;        // W_s[l][p][r]: strides of l and p (r unit-stride); <TR>: of r and p (l unit-stride)
   int64_t ldX;               // x_s[b][p]: row stride (p unit-stride)
   const double* partIn;      // the input's producer partials (nullptr: a network input)
   int32_t PIn, strideIn;
@@ -102,7 +119,23 @@ template <typename T> struct SweepSmallType;
 template <> struct SweepSmallType<float> { typedef uint32_t bits; typedef f32x4 acc; static constexpr int max_exp = kSweepSmallMaxExp; };
 template <> struct SweepSmallType<double> { typedef uint64_t bits; typedef f64x4 acc; static constexpr int max_exp = kSweep64MaxExp; };
 
-template <typename T, int DB, int P, bool TWO>
+// Transposed cores, float32: whole GROUPS of W in flight per wave (a 16-byte request is a group's four k-steps of one
+// (p, r-block)): a divisor of the DB groups of a site, one group where its 4 P DB MFMAs x 32 cycles cover an L2 hit (or
+// DB = 1 leaves no other divisor), else all DB - 64 registers (<4, 4>), 72 (<3, 2>) at the most
+template <int DB, int P>
+constexpr int sweep_small_queue_tr() { return P * DB >= 8 || DB == 1 ? 1 : DB; }
+
+typedef uint32_t sws_u32x4 __attribute__((ext_vector_type(4)));
+// one 16-byte request of a transposed float32 core: the lane's four values of l of a group (`from`: the core at the group's
+// first l, wave-uniform; `off`: the lane's own bytes), cleared where the group or the lane's row lies past D
+__device__ __forceinline__ f32x4 sweep_small_group(sw_gptr from, uint32_t off, uint32_t lmask, uint32_t cmask, bool last_g, bool last_q) {
+  sws_u32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) sws_u32x4*>(from + off);
+  if (last_g) v &= lmask;
+  if (last_q) v &= cmask;
+  return __builtin_bit_cast(f32x4, v);
+}
+
+template <typename T, int DB, int P, bool TWO, bool TR = false>
 __global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
   static_assert(DB >= 1 && DB <= 4 && (P == 2 || P == 4), "shape");
   constexpr bool F32 = sizeof(T) == 4;
@@ -112,6 +145,9 @@ __global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
   constexpr int NK = 4 * DB;                  // k-steps per site
   constexpr int SSQ = sweep_small_queue<DB, P>();
   static_assert(NK % SSQ == 0 && SSQ <= NK, "queue");
+  constexpr bool TRG = TR && F32;             // the queue holds groups (16-byte requests), not k-steps
+  constexpr int SG = sweep_small_queue_tr<DB, P>();
+  static_assert(DB % SG == 0, "queue of groups");
   const int lane = threadIdx.x;
   const int i16 = lane & 15, kg = lane >> 4;
   const int j = blockIdx.x, r = blockIdx.y;
@@ -168,13 +204,26 @@ __global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
   for (int p = 0; p < P; ++p)
 #pragma unroll
     for (int q = 0; q < DB; ++q) {
-      if constexpr (F32) voff[p][q] = (uint32_t)(((int64_t)p * a.ldWp + (q < DB - 1 || c_ok ? 16 * q + i16 : 0)) * 4);
+      if constexpr (TR) {
+        // transposed cores W_s[r][p][l], l unit-stride: the lane's ROW 16 q + i16 of r (stride ldWl) of every (p, r-block) -
+        // a row at or beyond D reads row 0 - and, float64, its position kg among a k-step's four values of l
+        const int64_t at = (int64_t)p * a.ldWp + (int64_t)(q < DB - 1 || c_ok ? 16 * q + i16 : 0) * a.ldWl;
+        voff[p][q] = F32 ? (uint32_t)(at * 4) : (uint32_t)((at + kg) * 8);
+      } else if constexpr (F32) voff[p][q] = (uint32_t)(((int64_t)p * a.ldWp + (q < DB - 1 || c_ok ? 16 * q + i16 : 0)) * 4);
       else voff[p][q] = (uint32_t)(((int64_t)p * a.ldWp + (q < DB - 1 || c_ok ? 16 * q + i16 : 0) + (int64_t)kg * a.ldWl) * 8);
     }
   bits_t lmask[4];                            // the last group's four k-steps (float64: the same in every lane)
   uint32_t kgoff, lko[4];                     // float32: the lane's row 4 kg of a group, and of the last group's k-steps
   int lrow[4];                                // float64: the first row of the last group's k-steps
-  if constexpr (F32) {
+  if constexpr (TRG) {
+    // the lane's four values of l of a group, 16 G + 4 kg + 0 .. 3, are 16 consecutive bytes of its row: valid or not as a
+    // whole in the last group (D % 4 == 0); an invalid lane reads the group's first four, which are < D
+    kgoff = 16u * (uint32_t)kg;
+    const bool l_ok = 16 * (DB - 1) + 4 * kg < D;
+    lmask[0] = l_ok ? ~0u : 0u;
+    lko[0] = l_ok ? kgoff : 0u;
+    asm volatile("" : "+v"(lmask[0]));
+  } else if constexpr (F32) {
     kgoff = (uint32_t)((int64_t)(4 * kg) * a.ldWl * 4);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -193,11 +242,12 @@ __global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
     }
   }
   asm volatile("" : "+v"(cmask));
-  const int64_t stepW = a.ldWl * ES;          // next row of l (bytes)
+  const int64_t stepW = TR ? ES : a.ldWl * ES;   // next value of l (bytes): a row of the core, or - transposed - an element
 
   sw_gptr Wcur = (sw_gptr)tp[a.site_ids[0]];
   sw_gptr Xcur = (sw_gptr)tp[a.site_ids[1]];
-  T wq[SSQ][P][DB];
+  // (transposed float32: SG whole groups, component t of an entry is its k-step t)
+  typename std::conditional<TRG, f32x4, T>::type wq[TRG ? SG : SSQ][P][DB];
   auto wrequest = [&](T (&dst)[P][DB], sw_gptr core, int u) {     // k-step u of `core` (u a compile-time value)
     const bool last_g = (u >> 2) == DB - 1;
     uint32_t ko = 0;                          // (float64: the lane's row is in voff)
@@ -218,8 +268,18 @@ __global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
         dst[p][q] = __builtin_bit_cast(T, v);
       }
   };
+  if constexpr (TRG) {
 #pragma unroll
-  for (int u = 0; u < SSQ; ++u) wrequest(wq[u], Wcur, u);
+    for (int G = 0; G < SG; ++G)
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int q = 0; q < DB; ++q)
+          wq[G][p][q] = sweep_small_group(Wcur + 64 * G, voff[p][q] + (G == DB - 1 ? lko[0] : kgoff), (uint32_t)lmask[0], (uint32_t)cmask, G == DB - 1, q == DB - 1);
+  } else {
+#pragma unroll
+    for (int u = 0; u < SSQ; ++u) wrequest(wq[u], Wcur, u);
+  }
 
   // a block's record of site s: the abs-sums of C and E' (each lane's own share, then over the lanes by shuffles in a
   // fixed order) and the exponent it applies.  Only the NEXT site's epilogue needs the exponent, so the six shuffle levels of
@@ -262,6 +322,30 @@ __global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
       for (int q = 0; q < DB; ++q)
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[p][q][e] = 0;
+    if constexpr (TRG) {
+      // a group at a time: the four k-steps of one (p, r-block) free its entry of the queue, which is requested again at
+      // once for SG groups on - every accumulator still meets its k-steps in the order u = 0 .. NK - 1
+#pragma unroll
+      for (int G = 0; G < DB; ++G) {
+#pragma unroll
+        for (int p = 0; p < P; ++p)
+#pragma unroll
+          for (int q = 0; q < DB; ++q) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+              acc[p][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[G % SG][p][q][t], st[G][t], acc[p][q], 0, 0, 0);
+            const int Gn = (G + SG) % DB;         // the group SG on: of this core, or of the next site's
+            wq[G % SG][p][q] = sweep_small_group((G + SG < DB ? Wcur : Wnext) + 64 * Gn, voff[p][q] + (Gn == DB - 1 ? lko[0] : kgoff),
+                                                 (uint32_t)lmask[0], (uint32_t)cmask, Gn == DB - 1, q == DB - 1);
+          }
+#pragma unroll
+        for (int lv = 0; lv < 6; ++lv)         // (the levels that the k-steps of this group carry in the forward kernel)
+          if (lv * NK / 6 >= 4 * G && lv * NK / 6 < 4 * G + 4) {
+            if (TWO) pendC += __shfl_xor(pendC, 32 >> lv, 64);
+            pendE += __shfl_xor(pendE, 32 >> lv, 64);
+          }
+      }
+    } else {
 #pragma unroll
     for (int u = 0; u < NK; ++u) {
 #pragma unroll
@@ -279,6 +363,7 @@ __global__ __launch_bounds__(64) void k_sweep_small(SweepSmallArgs a) {
           if (TWO) pendC += __shfl_xor(pendC, 32 >> lv, 64);
           pendE += __shfl_xor(pendE, 32 >> lv, 64);
         }
+    }
     }
     if (s > 0) {
       const int ex = record(s - 1, pendC, pendE, inv_s, false);   // (inv_s: still the one site s - 1 worked with)

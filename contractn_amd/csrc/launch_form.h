@@ -36,6 +36,8 @@ struct DevSwitches {
   int sweep_small64 = -1;  // CTN_SWEEP_SMALL64: 1 a float64 batched MPS of bond 8 ... 64 is walked in one launch (k_sweep_small<double>)
                          // wherever sweep_small_match takes it, k_sweep_f64 does not and neither CTN_SWEEP nor CTN_SWEEP64 is 0;
                          // 0 or unset: never (kSweepSmallF64Default).  CTN_SWEEP_SMALL does not reach a float64 plan, nor this a float32 one
+  int sweep_small_tr = 1;  // CTN_SWEEP_SMALL_TR=0: never a run of TRANSPOSED cores (the bond contracted with the state unit-stride:
+                         // k_sweep_small<.., TR = true>), which CTN_SWEEP_SMALL=1 / CTN_SWEEP_SMALL64=1 take as they take the forward ones
   int dot_tr = 1;        // CTN_DOT_TR=0: full dots against a transposed tensor stay on k_dot_split's 4-byte gathers
   int zip = -1;          // CTN_ZIP: 0 never fuse a zipper's two GEMM steps into one launch (k_zip_f32), 1 whenever the pair matches
                          // (tests), 2 likewise with 64 values of u per workgroup (k_zip64_f32).  fp64 plans: 1 the fp64 pair kernel
@@ -106,6 +108,7 @@ inline DevSwitches read_dev_switches() {
   d.sweep64 = num("CTN_SWEEP64", 1);
   d.sweep_small = num("CTN_SWEEP_SMALL", -1);
   d.sweep_small64 = num("CTN_SWEEP_SMALL64", -1);
+  d.sweep_small_tr = num("CTN_SWEEP_SMALL_TR", 1);
   d.lat64_min_k = num("CTN_LAT64_MIN_K", 512);
   d.splitk_fill_long = num("CTN_SPLITK_FILL_LONG", 2);
   d.lat_max_t = num("CTN_LAT_MAX_T", 64);

@@ -15,9 +15,17 @@ tests/test_gpu_sweep_small_elements.py is the correctness check.
 tests/sweep_cases_small_f64.py, default --out profiles/sweep_small_f64_ab.json): the same six shapes, sites, rounds and
 ``ahead`` rule; tests/test_gpu_sweep_small_f64.py is its correctness check.
 
+``--transposed`` (either --dtype) measures the same shapes with the cores stored TRANSPOSED (tests/sweep_cases_small_tr.py,
+layout "prl": the bond contracted with the state unit-stride; k_sweep_small<.., TR = true>) against TWO baselines in the
+same alternation: ``unset`` - the switch-unset path on the same plan, what such a network gets without the form - and
+``forward`` - the forward kernel under the switch on the forward twin of the network, the same values with the cores
+stored the other way round.  ``behind_forward``: whether the transposed median is ABOVE the forward one by more than the
+larger spread.  Default --out profiles/sweep_small_tr_ab.json / sweep_small_tr_f64_ab.json;
+tests/test_gpu_sweep_small_tr.py is the correctness check.
+
 Run it under a time limit of its own (`timeout -k 10 420 python tools/sweep_small_timing.py`): it takes about a minute.
 
-    python tools/sweep_small_timing.py [--dtype f32|f64] [--sites 100] [--rounds 5] [--reps 300] [--warmup 5] [--out FILE]
+    python tools/sweep_small_timing.py [--dtype f32|f64] [--transposed] [--sites 100] [--rounds 5] [--reps 300] [--warmup 5] [--out FILE]
 """
 import argparse
 import json
@@ -35,6 +43,7 @@ import torch  # noqa: E402
 from contractn_amd import einsum as E  # noqa: E402
 from tests import sweep_cases_small as C  # noqa: E402
 from tests import sweep_cases_small_f64 as C64  # noqa: E402
+from tests import sweep_cases_small_tr as CT  # noqa: E402
 
 SHAPES = [(16, 2, 256), (32, 2, 256), (32, 2, 1024), (32, 2, 4096), (64, 2, 256), (48, 4, 1024)]      # (D, P, B)
 
@@ -67,32 +76,40 @@ def one_round(bc, ins, outs, reps):
     return float(np.median(wall))
 
 
-def measure(D, P, B, sites, rounds, reps, warmup, dtype="f32"):
+def measure(D, P, B, sites, rounds, reps, warmup, dtype="f32", transposed=False):
     key, np_dtype, torch_dtype, operands, is_two = DTYPES[dtype]
     on = key + "=1"
-    net = C.Net(D, P, B, sites, "plr", "produced")
-    dev_ops = [torch.from_numpy(np.ascontiguousarray(o)).cuda() for o in operands(net)]
-    torch.cuda.synchronize()
+    fwd_net = C.Net(D, P, B, sites, "plr", "produced")
+    net = CT.TrNet.of(fwd_net) if transposed else fwd_net
+    fwd_ops = operands(fwd_net)
+    dev_ops = [torch.from_numpy(np.ascontiguousarray(o)).cuda() for o in (net.stored(fwd_ops) if transposed else fwd_ops)]
     ins = [o.data_ptr() for o in dev_ops]
     modes = {on: executor(net, "1", key, np_dtype), "unset": executor(net, None, key, np_dtype)}
+    mode_ins = {k: ins for k in modes}
+    if transposed:                               # the forward kernel on the forward twin: the same values, the cores the other way round
+        dev_fwd = [torch.from_numpy(np.ascontiguousarray(o)).cuda() for o in fwd_ops]
+        modes["forward"], mode_ins["forward"] = executor(fwd_net, "1", key, np_dtype), [o.data_ptr() for o in dev_fwd]
+    torch.cuda.synchronize()
     outs = {k: torch.empty(net.out_shape, dtype=torch_dtype, device="cuda") for k in modes}
     res = {"shape": {"D": D, "P": P, "B": B, "sites": sites}, "two_step_plan": bool(is_two(net))}
     if dtype != "f32":
         res["dtype"] = dtype
+    if transposed:
+        res["transposed"] = net.layout
     try:
         for k, bc in modes.items():
             for _ in range(warmup):
-                bc.enqueue(ins, [outs[k].data_ptr()])
+                bc.enqueue(mode_ins[k], [outs[k].data_ptr()])
                 bc.executor.fetch()
         per = {k: [] for k in modes}
         for _ in range(rounds):
-            for k, bc in modes.items():              # alternate: the switch, then unset, every round
-                per[k].append(one_round(bc, ins, [outs[k].data_ptr()], reps))
+            for k, bc in modes.items():              # alternate: the switch, then unset (then the forward twin), every round
+                per[k].append(one_round(bc, mode_ins[k], [outs[k].data_ptr()], reps))
         for k, bc in modes.items():
             bc.executor.fetch()
             bc.executor.set_timing(4)
             for _ in range(4):
-                bc.enqueue(ins, [outs[k].data_ptr()])
+                bc.enqueue(mode_ins[k], [outs[k].data_ptr()])
             step_ms = np.asarray(bc.executor.step_ms(), dtype=np.float64)
             bc.executor.set_timing(0)
             ms = np.asarray(per[k])
@@ -103,6 +120,10 @@ def measure(D, P, B, sites, rounds, reps, warmup, dtype="f32"):
         res["ahead"] = bool(b["median_ms"] - a["median_ms"] > max(a["spread_ms"], b["spread_ms"]))
         same = torch.allclose(outs[on], outs["unset"], rtol=1e-3, atol=1e-5 * float(outs["unset"].abs().max()))
         res["results_agree_1e-3"] = bool(same)
+        if transposed:
+            f = res["forward"]
+            res["behind_forward"] = bool(a["median_ms"] - f["median_ms"] > max(a["spread_ms"], f["spread_ms"]))
+            res["same_bits_as_forward"] = bool(torch.equal(outs[on], outs["forward"]))
     finally:
         for bc in modes.values():
             bc.executor.close()
@@ -117,15 +138,16 @@ def main():
     ap.add_argument("--reps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
+    ap.add_argument("--transposed", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "sweep_small_ab.json" if a.dtype == "f32" else "sweep_small_f64_ab.json")
+        a.out = os.path.join(ROOT, "profiles", "sweep_small%s%s_ab.json" % ("_tr" if a.transposed else "", "" if a.dtype == "f32" else "_f64"))
     if not torch.cuda.is_available():
         sys.exit("sweep_small_timing: no GPU - a time is measured on the device or not at all")
     lines = []
     for D, P, B in SHAPES:
-        lines.append(measure(D, P, B, a.sites, a.rounds, a.reps, a.warmup, a.dtype))
+        lines.append(measure(D, P, B, a.sites, a.rounds, a.reps, a.warmup, a.dtype, a.transposed))
         print(json.dumps(lines[-1]), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
