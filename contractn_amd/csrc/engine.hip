@@ -132,6 +132,8 @@ struct Exec {
   int32_t* d_sweep_e = nullptr;        // float64: [R][S][J] exponents of the blocks' scales (d_sweep_a: [R][2 S][J], d_sweep_z: [R][2 S])
   std::vector<int32_t> launched_form;  // per step: ctn_step_form of the last enqueue (ctn_exec_step_form), else 0
   std::vector<int32_t> launched_tile;  // per step: (tile rows << 16 | tile columns) of the last enqueue's MFMA kernel, else 0
+  std::vector<int32_t> graph_form, graph_tile;   // what the captured sequence reported (a replay runs no host code) ...
+  bool report_is_graphs = false;       // ... and whether launched_form / launched_tile hold exactly that
   char* d_ws = nullptr;
   int32_t* d_tables = nullptr;
   int64_t* d_tables64 = nullptr;    // batch / outer-group offsets (Plan::tables64)
@@ -1148,6 +1150,11 @@ static int launch_finish(Exec* E, const RunClose* close = nullptr) {
 static int exec_launch_steps(Exec* E, const RunClose* close = nullptr) {
   const Plan& P = *E->plan;
   int rc = CTN_OK;
+  // the report is of THIS enqueue: a step that reports nothing now (a streaming step, a member that stepped aside for the
+  // eager mode) must not keep the mark of an earlier one
+  std::fill(E->launched_tile.begin(), E->launched_tile.end(), 0);
+  std::fill(E->launched_form.begin(), E->launched_form.end(), 0);
+  E->report_is_graphs = false;
   if (P.chain && E->d_chain != nullptr) {
     rc = launch_chain(E);
   } else {
@@ -1225,6 +1232,12 @@ static int exec_launch_all(Exec* E, const RunClose* close = nullptr) {
     }
     (void)hipGraphDestroy(g);
     E->graph_aligned = E->outs_aligned16;
+    E->graph_form = E->launched_form; E->graph_tile = E->launched_tile;
+    E->report_is_graphs = true;
+  }
+  if (!E->report_is_graphs) {                  // an eager repeat (exec_fetch_checked) reported its own launches in between
+    E->launched_form = E->graph_form; E->launched_tile = E->graph_tile;
+    E->report_is_graphs = true;
   }
   HIPCHECK(hipGraphLaunch(E->graph_exec, E->stream));
   return CTN_OK;
@@ -1573,7 +1586,12 @@ static bool exec_scales_suspect(const Exec* E, const double* resc = nullptr, int
       if (st.kernel == CTN_KERNEL_FUSED) continue;
       const Role role = E->forms.role[s];
       if (role == Role::Absorbed) continue;                          // runs inside a later step's launch
-      if (E->forms.sweep_role[s] && !E->eager_rescale) {             // a sweep keeps its products in range by itself
+      // A sweep rescales inside its launch, so its members' factors say nothing about its accumulators - and those are NOT
+      // in range by themselves: the state stays un-rescaled and a block's scale goes into the next site's weights, so W_s .
+      // state carries one core more than any product of the reference.  The sweep raises its own alarm:
+      // a block whose state left the range records a non-finite abs-sum, and the bookkeeping (k_sweep_z / k_sweep64_z,
+      // k_sweep_finish / k_sweep64_finish) turns that into a non-finite factor of the step.
+      if (E->forms.sweep_role[s] && !E->eager_rescale) {
         if (!std::isfinite(rs[s])) return true;
         continue;
       }

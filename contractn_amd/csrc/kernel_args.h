@@ -96,12 +96,14 @@ struct FinalArgs {
 // ---------------------------------------------------------------------------
 // Rescale factor of a tensor from its producer's partial sums (reference
 // einsum.py:97-102: norm = sum|T|, rescale = norm / numel, applied iff
-// norm > min_norm).  All 64 lanes of the calling wave must be active.
+// norm > min_norm).  All 64 lanes of the calling wave must be active.  `nan_out`: whether the abs-sum is NaN - a product
+// that went to inf - inf or 0 x inf somewhere; the comparison above then fails like the reference's own would.
 template <typename T>
 __device__ __forceinline__ T producer_scale(const double* part, int P, int stride, double numel, double min_norm,
-                                            int r, bool* cond_out = nullptr) {
+                                            int r, bool* cond_out = nullptr, bool* nan_out = nullptr) {
   if (part == nullptr) {
     if (cond_out) *cond_out = false;
+    if (nan_out) *nan_out = false;
     return (T)1;
   }
   const int lane = threadIdx.x & 63;
@@ -125,6 +127,7 @@ __device__ __forceinline__ T producer_scale(const double* part, int P, int strid
   const T norm = (T)v;
   const bool cond = norm > (T)min_norm;
   if (cond_out) *cond_out = cond;
+  if (nan_out) *nan_out = v != v;
   return cond ? norm / (T)numel : (T)1;
 }
 

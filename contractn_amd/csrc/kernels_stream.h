@@ -461,20 +461,24 @@ __global__ __launch_bounds__(256) void k_collapse(const double* scratch, int blo
 // ---------------------------------------------------------------------------
 // Finishing passes.  k_scales: one wave per (step, replica) turns the step's partials into its
 // rescale factor (0.0 = not rescaled) and log(rescale) evaluated in the tensor dtype
-// (reference einsum.py:97-106).  k_finalize: normalise the final tensor and sum the logs.
+// (reference einsum.py:97-106).  A NaN abs-sum is no rescale either, as in the reference - but the factor is reported
+// as NaN, not 0.0: in the lazy mode the NaN may be an accumulator's (inf - inf, 0 x inf on un-normalised operands) where
+// every normalised quantity is finite, and a 0.0 would tell the range guard of the fetch "a tensor of zeros"
+// (engine.hip, exec_scales_suspect: a non-finite factor repeats the run eagerly).  k_finalize: normalise the final
+// tensor and sum the logs.
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void k_scales(FinalArgs f, double* __restrict__ logs) {
   const int r = blockIdx.y;
   const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (s >= f.n_steps) return;  // whole wave exits together
-  bool cond = false;
+  bool cond = false, bad = false;
   T sc = (T)1;
   if (f.stabilize)
     sc = producer_scale<T>(f.partials + (size_t)f.stepOff[s] * f.R, f.stepP[s], f.stepSlots[s], f.stepNumel[s],
-                           f.min_norm, r, &cond);
+                           f.min_norm, r, &cond, &bad);
   if ((threadIdx.x & 63) == 0) {
-    f.rescales[(size_t)r * f.n_steps + s] = cond ? (double)sc : 0.0;
+    f.rescales[(size_t)r * f.n_steps + s] = cond ? (double)sc : bad ? (double)NAN : 0.0;
     logs[(size_t)r * f.n_steps + s] = cond ? (double)log(sc) : 0.0;
   }
 }
@@ -491,7 +495,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinalArgs f, const double* __r
   }
   if (!f.stabilize || f.defer) return;
   const double rl = f.rescales[(size_t)r * f.n_steps + f.n_steps - 1];
-  if (rl == 0.0) return;  // last step was not rescaled (norm <= min_norm): tensor unchanged
+  if (rl == 0.0 || rl != rl) return;  // last step was not rescaled (norm <= min_norm, or NaN): tensor unchanged
   const T s_last = (T)rl;
   T* out = (T*)f.ptrs[(size_t)r * f.n_tensors + f.id_out];
   constexpr int V = 16 / (int)sizeof(T);
@@ -516,7 +520,7 @@ __global__ __launch_bounds__(256) void k_finish(void* const* __restrict__ ptrs, 
                                                 const double* __restrict__ mult, int vec) {
   const int r = blockIdx.y;
   const double rl = stabilize ? rescales[(size_t)r * n_steps + n_steps - 1] : 0.0;
-  const bool div = rl != 0.0;
+  const bool div = rl != 0.0 && rl == rl;
   const T s_last = div ? (T)rl : (T)1, m = (T)mult[r];
   T* out = (T*)ptrs[(size_t)r * n_tensors + id_out];
   constexpr int V = 16 / (int)sizeof(T);

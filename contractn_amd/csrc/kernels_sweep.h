@@ -305,19 +305,29 @@ __global__ __launch_bounds__(D == 64 ? 256 : 512, 1) void k_sweep_f32(SweepArgs 
 // that walks the sites and takes one of them per site spends 70 us on a 100-site chain; every transcendental below is
 // evaluated once, in parallel, and the walks over the sites only add and compare.)
 //
-// k_sweep_logs: la[s][j] = log a[s][j] (-inf for an all-zero block), ls[s][j] = log s[s][j].  grid (S, R), 256 threads.
+// The sweep's own range.  k_sweep_f32 keeps the state un-rescaled and folds a block's scale into the NEXT site's weights, so
+// its accumulators W_s . state carry one core more than anything the reference ever forms: they can leave
+// the type's range where every normalised quantity is fine.  The alarm is the record: a block whose state went to inf or NaN
+// records a non-finite abs-sum (and, past the float range, a non-finite scale).  A non-finite record is NaN below, a NaN
+// anywhere makes Z_s NaN, and a NaN Z_s leaves INFINITY in the step's slot: k_scales then reports a non-finite factor and
+// the fetch repeats the run with the per-site launches (engine.hip, exec_scales_suspect) - k_sweep64_z's kBad rule.
+// -inf keeps meaning "all zero".
+//
+// k_sweep_logs: la[s][j] = log a[s][j] (-inf for an all-zero block), ls[s][j] = log s[s][j]; NaN for a non-finite record.
+// grid (S, R), 256 threads.
 __global__ __launch_bounds__(256) void k_sweep_logs(const double* __restrict__ rec_a, const float* __restrict__ rec_s, int S, int J,
                                                     double* __restrict__ la, double* __restrict__ ls) {
   const size_t base = ((size_t)blockIdx.y * S + blockIdx.x) * J;
   for (int j = threadIdx.x; j < J; j += 256) {
-    const double av = rec_a[base + j];
-    la[base + j] = av > 0.0 ? log(av) : -INFINITY;
-    ls[base + j] = log((double)rec_s[base + j]);
+    const double av = rec_a[base + j], sv = (double)rec_s[base + j];
+    la[base + j] = !(av < INFINITY) ? NAN : av > 0.0 ? log(av) : -INFINITY;
+    ls[base + j] = (sv > 0.0 && sv < INFINITY) ? log(sv) : NAN;
   }
 }
 
 // k_sweep_z: Z_s = log of the whole tensor's mean |.| after site s, a log-sum-exp over the blocks of
-// la[s][j] + sum_{i < s} ls[i][j] (see k_sweep_f32).  grid (S, R), 256 threads; fixed-order sums.
+// la[s][j] + sum_{i < s} ls[i][j] (see k_sweep_f32); NaN when a record behind any of its terms is non-finite.
+// grid (S, R), 256 threads; fixed-order sums.
 __global__ __launch_bounds__(256) void k_sweep_z(const double* __restrict__ la, const double* __restrict__ ls, int S, int J,
                                                  double numel, double* __restrict__ Z) {
   __shared__ double red[4];
@@ -328,7 +338,8 @@ __global__ __launch_bounds__(256) void k_sweep_z(const double* __restrict__ la, 
   for (int j = threadIdx.x; j < J; j += 256) {
     double g = 0.0;
     for (int i = 0; i < s; ++i) g += ps[(size_t)i * J + j];
-    mx = fmax(mx, pa[j] + g);
+    const double t = pa[j] + g;
+    mx = fmax(mx, t == t ? t : INFINITY);     // (fmax drops a NaN: a bad term goes on as +inf, which no good one is)
   }
 #pragma unroll
   for (int of = 32; of > 0; of >>= 1) mx = fmax(mx, __shfl_xor(mx, of, 64));
@@ -336,8 +347,8 @@ __global__ __launch_bounds__(256) void k_sweep_z(const double* __restrict__ la, 
   __syncthreads();
   mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
   __syncthreads();
-  if (mx == -INFINITY) {                      // an all-zero tensor
-    if (threadIdx.x == 0) Z[(size_t)r * S + s] = -INFINITY;
+  if (mx == -INFINITY || mx == INFINITY) {    // an all-zero tensor; a non-finite record (uniform over the workgroup)
+    if (threadIdx.x == 0) Z[(size_t)r * S + s] = mx < 0.0 ? -INFINITY : NAN;
     return;
   }
   double sum = 0.0;
@@ -374,7 +385,8 @@ __global__ __launch_bounds__(256) void k_sweep_finish(SweepFinish f) {
   const double* Z = f.Z + (size_t)r * f.S;
   if (threadIdx.x == 0) {
     // the reference's recurrence (einsum.py:97-106 over the chain's steps), in logs: norm_s = numel exp(Z_s) / R_{s-1};
-    // rescaled iff norm_s > min_norm, then R_s = exp(Z_s)
+    // rescaled iff norm_s > min_norm, then R_s = exp(Z_s).  A NaN Z_s (a non-finite record) gives a NaN norm_s: no
+    // comparison holds, R stays, and the slot below gets INFINITY
     const double lnum = log(f.numel), lmin = f.min_norm > 0.0 ? log(f.min_norm) : -INFINITY;
     double logR = 0.0, logR_before_last = 0.0;
     for (int s = 0; s < f.S; ++s) {
@@ -393,7 +405,8 @@ __global__ __launch_bounds__(256) void k_sweep_finish(SweepFinish f) {
   if (j == 0) {                               // what each step's own launch would have left: its abs-sum, in slot 0
     for (int s = threadIdx.x; s < f.S; s += 256) {
       double* dst = f.partials + (size_t)f.part_off[s] * f.R + (size_t)r * f.part_slots[s];
-      dst[0] = lognorm[s] == -INFINITY ? 0.0 : exp(lognorm[s]);
+      const double ln = lognorm[s];
+      dst[0] = ln == -INFINITY ? 0.0 : ln != ln ? INFINITY : exp(ln);
       for (int i = 1; i < f.part_slots[s]; ++i) dst[i] = 0.0;
     }
   }
