@@ -28,6 +28,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "plan.h"
@@ -478,131 +479,105 @@ static void launch_group(Exec* E, const LeafGroup& G) {
 // the scale bookkeeping behind a sweep kernel that leaves the records of k_sweep_f64 (rec_a, rec_e): the members' rescale
 // factors, then the result's rows at their common scale.  <T, TWO>: the rows' element type; two member steps per site or one
 template <typename T, bool TWO>
-static void launch_sweep64_finish(Exec* E, int s) {
+static void launch_sweep64_finish(Exec* E) {
   const Plan& P = *E->plan;
-  const Step& st = P.steps[s];
   const int R = E->R;
   const SweepDesc& sd = E->forms.sweep;
-  const int S = (int)sd.steps.size() / (TWO ? 2 : 1);
-  const double numelE = (double)P.tensors[st.out].numel, numelC = numelE * sd.Pd;
+  const int S = sd.sites();
+  const double numelE = (double)P.tensors[sd.idOut].numel, numelC = numelE * sd.Pd;
   hipLaunchKernelGGL(k_sweep64_z<TWO>, dim3((unsigned)sd.steps.size(), (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
                      (const int32_t*)E->d_sweep_e, S, sd.J, numelC, numelE, E->d_sweep_z);
   Sweep64Finish f{};
-  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = sd.idOut; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
   f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.rec_e = E->d_sweep_e; f.part_off = E->d_sweep_off;
   f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numelC = numelC; f.numelE = numelE;
   f.min_norm = P.stabilize ? P.min_norm : INFINITY;
   hipLaunchKernelGGL((k_sweep64_finish<T, TWO>), dim3((unsigned)sd.J, (unsigned)R), dim3(256), 0, E->stream, f);
 }
 
-// the last member of a float64 sweep: 2 S member steps, S sites
-static int launch_sweep64(Exec* E, int s) {
-  const Plan& P = *E->plan;
-  const Step& st = P.steps[s];
-  const int R = E->R;
+// What the argument structs of the three sweep kernels share (SweepArgs, Sweep64Args, SweepSmallArgs: the same field
+// names), filled from the descriptor alone - and the tile the run reports at its last member s: 16 rows x all columns of
+// C (1024 at bond 256, d = 4) per workgroup, every site
+template <typename Args>
+static Args sweep_args(Exec* E, int s) {
   const SweepDesc& sd = E->forms.sweep;
-  const int S = (int)sd.steps.size() / 2;
-  Sweep64Args w{};
+  Args w{};
   w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
-  w.idIn = sd.idIn; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M;
+  w.idIn = sd.idIn; w.idOut = sd.idOut; w.S = sd.sites(); w.J = sd.J; w.M = sd.M;
   w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
   producer_partials(E, sd.idIn, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
-  w.min_norm = P.min_norm;
-  w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
-  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns of C per workgroup, every site
-  {
-    const dim3 gs((unsigned)sd.J, (unsigned)R);
-#define CTN_SWEEP64_LAUNCH(DD)                                                                                        \
-    do {                                                                                                              \
-      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_f64<DD, 4>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);      \
-      else hipLaunchKernelGGL((k_sweep_f64<DD, 2>), gs, dim3(Sweep64Shape<DD>::NT), 0, E->stream, w);                 \
-    } while (0)
-    if (sd.D == 64) CTN_SWEEP64_LAUNCH(64);
-    else if (sd.D == 128) CTN_SWEEP64_LAUNCH(128);
-    else if (sd.D == 256) CTN_SWEEP64_LAUNCH(256);
-    else CTN_SWEEP64_LAUNCH(512);
-#undef CTN_SWEEP64_LAUNCH
-  }
-  launch_sweep64_finish<double, true>(E, s);
-  return CTN_OK;
+  w.min_norm = E->plan->min_norm;
+  w.rec_a = E->d_sweep_a;
+  report_tile(E, s, SWR, sd.D * sd.Pd);
+  return w;
 }
 
-// the last member of a small-bond sweep (float: CTN_SWEEP_SMALL=1, double: CTN_SWEEP_SMALL64=1): S sites of two member
-// steps each (`two`; double always) or of one; `tr`: the cores are stored with the contracted bond unit-stride
-template <typename T, bool TWO>
-static int launch_sweep_small(Exec* E, int s) {
-  const Plan& P = *E->plan;
-  const Step& st = P.steps[s];
-  const int R = E->R;
-  const SweepDesc& sd = E->forms.sweep;
-  SweepSmallArgs w{};
-  w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
-  w.idIn = sd.idIn; w.idOut = st.out; w.S = (int)sd.steps.size() / (TWO ? 2 : 1); w.J = sd.J; w.M = sd.M; w.D = sd.D;
-  w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
-  producer_partials(E, sd.idIn, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
-  w.min_norm = P.min_norm;
-  w.rec_a = E->d_sweep_a; w.rec_e = E->d_sweep_e;
-  E->launched_form[s] = sizeof(T) == 4 ? CTN_FORM_SWEEP_SMALL : CTN_FORM_SWEEP_SMALL_F64;
-  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns of C per wave, every site
-  {
-    const dim3 gs((unsigned)sd.J, (unsigned)R);
-    const int DB = (sd.D + 15) / 16;
-#define CTN_SWEEP_SMALL_LAUNCH(BB)                                                                          \
-    do {                                                                                                    \
-      if (sd.tr) {                                                                                          \
-        if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small<T, BB, 4, TWO, true>), gs, dim3(64), 0, E->stream, w);  \
-        else hipLaunchKernelGGL((k_sweep_small<T, BB, 2, TWO, true>), gs, dim3(64), 0, E->stream, w);       \
-      } else if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_small<T, BB, 4, TWO>), gs, dim3(64), 0, E->stream, w);   \
-      else hipLaunchKernelGGL((k_sweep_small<T, BB, 2, TWO>), gs, dim3(64), 0, E->stream, w);               \
-    } while (0)
-    if (DB == 1) CTN_SWEEP_SMALL_LAUNCH(1);
-    else if (DB == 2) CTN_SWEEP_SMALL_LAUNCH(2);
-    else if (DB == 3) CTN_SWEEP_SMALL_LAUNCH(3);
-    else CTN_SWEEP_SMALL_LAUNCH(4);
-#undef CTN_SWEEP_SMALL_LAUNCH
-  }
-  launch_sweep64_finish<T, TWO>(E, s);
-  return CTN_OK;
+// The ONE ladder behind the sweep kernels' instantiations: f(I, P) with the run-time bond index i = 0 .. 3 and physical
+// dimension 2 or 4 as std::integral_constant arguments
+template <typename F>
+static void sweep_pick(int i, int Pd, F f) {
+  auto bond = [&](auto P) {
+    if (i == 0) f(std::integral_constant<int, 0>(), P);
+    else if (i == 1) f(std::integral_constant<int, 1>(), P);
+    else if (i == 2) f(std::integral_constant<int, 2>(), P);
+    else f(std::integral_constant<int, 3>(), P);
+  };
+  if (Pd == 4) bond(std::integral_constant<int, 4>());
+  else bond(std::integral_constant<int, 2>());
 }
 
-// the last member of a sweep: the whole chain, then its scale bookkeeping
-static int launch_sweep(Exec* E, int s) {
-  const Plan& P = *E->plan;
-  const Step& st = P.steps[s];
+// the last member of a sweep: the whole chain in one launch, then its scale bookkeeping
+static int launch_sweep_run(Exec* E, int s) {
   const int R = E->R;
   const SweepDesc& sd = E->forms.sweep;
-  const int S = (int)sd.steps.size();
-  const Step& f0 = P.steps[sd.steps.front()];
-  SweepArgs w{};
-  w.ptrs = E->d_ptrs; w.n_tensors = E->n_tensors; w.site_ids = E->d_sweep_ids;
-  w.idIn = f0.lhs; w.idOut = st.out; w.S = S; w.J = sd.J; w.M = sd.M;
-  w.ldIn = sd.ldIn; w.ldOut = sd.ldOut; w.ldWl = sd.ldWl; w.ldWp = sd.ldWp; w.ldX = sd.ldX;
-  producer_partials(E, f0.lhs, &w.partIn, &w.PIn, &w.strideIn, &w.numelIn);
-  w.min_norm = P.min_norm;
-  w.rec_a = E->d_sweep_a; w.rec_s = E->d_sweep_s; w.dbg = nullptr;
-  report_tile(E, s, SWR, sd.D * sd.Pd);   // 16 rows x all columns (1024 at bond 256, d = 4) per workgroup, every site
+  const dim3 gs((unsigned)sd.J, (unsigned)R);
+  if (sd.small) {
+    // small bonds (float: CTN_SWEEP_SMALL=1, double: CTN_SWEEP_SMALL64=1): 16 values of the bond per index step, one wave per
+    // workgroup; `tr`: the cores are stored with the contracted bond unit-stride
+    SweepSmallArgs w = sweep_args<SweepSmallArgs>(E, s);
+    w.D = sd.D; w.rec_e = E->d_sweep_e;
+    E->launched_form[s] = sd.f64 ? CTN_FORM_SWEEP_SMALL_F64 : CTN_FORM_SWEEP_SMALL;
+    // <T, TWO>: S sites of two member steps each (double always) or of one
+    auto run = [&](auto t, auto two) {
+      using T = decltype(t);
+      sweep_pick((sd.D + 15) / 16 - 1, sd.Pd, [&](auto I, auto P) {
+        if (sd.tr) hipLaunchKernelGGL((k_sweep_small<T, I() + 1, P(), two(), true>), gs, dim3(64), 0, E->stream, w);
+        else hipLaunchKernelGGL((k_sweep_small<T, I() + 1, P(), two()>), gs, dim3(64), 0, E->stream, w);
+      });
+      launch_sweep64_finish<T, two()>(E);
+    };
+    if (sd.f64) run(double(), std::true_type());
+    else if (sd.two) run(float(), std::true_type());
+    else run(float(), std::false_type());
+    return CTN_OK;
+  }
+  const int ib = sd.D == 64 ? 0 : sd.D == 128 ? 1 : sd.D == 256 ? 2 : 3;       // bond 64 << ib
+  if (sd.f64) {
+    // float64: 2 S member steps, S sites
+    Sweep64Args w = sweep_args<Sweep64Args>(E, s);
+    w.rec_e = E->d_sweep_e;
+    sweep_pick(ib, sd.Pd, [&](auto I, auto P) {
+      hipLaunchKernelGGL((k_sweep_f64<(64 << I()), P()>), gs, dim3(Sweep64Shape<(64 << I())>::NT), 0, E->stream, w);
+    });
+    launch_sweep64_finish<double, true>(E);
+    return CTN_OK;
+  }
+  const Plan& P = *E->plan;
+  const int S = sd.sites();
+  SweepArgs w = sweep_args<SweepArgs>(E, s);
+  w.rec_s = E->d_sweep_s; w.dbg = nullptr;
   const int rc = stamp_buffer(E, s, (size_t)sd.J * R, &w.dbg);
   if (rc != CTN_OK) return rc;
-  {
-    const dim3 gs((unsigned)sd.J, (unsigned)R);
-#define CTN_SWEEP_LAUNCH(DD)                                                                                      \
-    do {                                                                                                          \
-      if (sd.Pd == 4) hipLaunchKernelGGL((k_sweep_f32<DD, 4>), gs, dim3(DD == 64 ? 256 : 512), 0, E->stream, w);  \
-      else hipLaunchKernelGGL((k_sweep_f32<DD, 2>), gs, dim3(DD == 64 ? 256 : 512), 0, E->stream, w);             \
-    } while (0)
-    if (sd.D == 64) CTN_SWEEP_LAUNCH(64);
-    else if (sd.D == 128) CTN_SWEEP_LAUNCH(128);
-    else if (sd.D == 256) CTN_SWEEP_LAUNCH(256);
-    else CTN_SWEEP_LAUNCH(512);
-#undef CTN_SWEEP_LAUNCH
-  }
-  const double numel = (double)P.tensors[st.out].numel;
+  sweep_pick(ib, sd.Pd, [&](auto I, auto Pd) {
+    hipLaunchKernelGGL((k_sweep_f32<(64 << I()), Pd()>), gs, dim3(I() == 0 ? 256 : 512), 0, E->stream, w);
+  });
+  const double numel = (double)P.tensors[sd.idOut].numel;
   hipLaunchKernelGGL(k_sweep_logs, dim3((unsigned)S, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_a,
                      (const float*)E->d_sweep_s, S, sd.J, E->d_sweep_la, E->d_sweep_ls);
   hipLaunchKernelGGL(k_sweep_z, dim3((unsigned)S, (unsigned)R), dim3(256), 0, E->stream, (const double*)E->d_sweep_la,
                      (const double*)E->d_sweep_ls, S, sd.J, numel, E->d_sweep_z);
   SweepFinish f{};
-  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = st.out; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
+  f.ptrs = E->d_ptrs; f.n_tensors = E->n_tensors; f.idOut = sd.idOut; f.S = S; f.J = sd.J; f.R = R; f.D = sd.D; f.M = sd.M;
   f.ldOut = sd.ldOut; f.Z = E->d_sweep_z; f.ls = E->d_sweep_ls; f.part_off = E->d_sweep_off;
   f.part_slots = E->d_sweep_slots; f.partials = E->d_partials; f.numel = numel;
   f.min_norm = P.stabilize ? P.min_norm : INFINITY;
@@ -615,9 +590,7 @@ static int launch_sweep_member(Exec* E, int s) {
   if (E->forms.sweep_role[s] == 1) return mark_absorbed(E, s);
   const StepTimer t(E, s);
   if (t.rc != CTN_OK) return t.rc;
-  const SweepDesc& sd = E->forms.sweep;
-  const int rc = sd.small ? (sd.f64 ? launch_sweep_small<double, true>(E, s) : sd.two ? launch_sweep_small<float, true>(E, s) : launch_sweep_small<float, false>(E, s))
-                          : sd.f64 ? launch_sweep64(E, s) : launch_sweep(E, s);
+  const int rc = launch_sweep_run(E, s);
   return rc != CTN_OK ? rc : t.end();
 }
 
@@ -1401,7 +1374,7 @@ int ctn_exec_create(const ctn_plan* plan, int device, void* stream, int replicas
   Exec& E = x->e;
   E.sw = read_dev_switches();
   // (a small-bond sweep that is asked for takes a chain plan from the chain walker: the executor works on its own copy)
-  if (sweep_small_unchains(plan->p, E.sw)) E.own_plan = unchained(plan->p);
+  if (sweep_small_unchains(plan->p, replicas, n_cu > 0 ? n_cu : 256, E.sw)) E.own_plan = unchained(plan->p);
   const Plan& P = E.own_plan.n_steps ? E.own_plan : plan->p;
   E.plan = &P; E.device = device; E.R = replicas; E.n_cu = n_cu > 0 ? n_cu : 256;
   E.use_graph = E.sw.graph;

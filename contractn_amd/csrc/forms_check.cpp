@@ -11,6 +11,7 @@
 // workspace, with rows n elements apart (a two-step run; n = the input's own row stride must stay taken, any other refused).
 // On a float64 plan the run is the one the same matcher finds there.  W_LDL=<n> likewise: the l stride of every core of that
 // float64 run becomes n (dense network inputs never have an odd one; the cores' own stride must stay taken).
+// DESC=1 is no switch either: it appends the `desc=` field below to the line, which is otherwise byte for byte the same.
 // For every plan and every setting one line goes to stdout with everything an executor would
 // decide when it is created:
 //
@@ -20,6 +21,8 @@
 //     bufs=slab:<n>,fold:<n>,zl:<n>,group:<n>,sweep:<a>/<s>/<z>/<l>/<e>,tabs:<n>
 //     sweep=[<member steps,..>]<f32|f64|small2|small1|small2f64|->[/tr: a small run of transposed cores] ares=[<step>:<ntw>,..] dot=[<step>,..] groups=[<head>:<len>,..]
 //     side=[<tensor>:<buffer>,..]x<bytes>x<buffers> ok | <the invariant that failed>
+//     [DESC=1: desc=in<idIn>/out<idOut>/S<sites>/J<J>/M<M>/D<D>/P<Pd>/ld<In,Out,Wl,Wp,X>/ids<W_1,x_1,..>/offs<..>/slots<..> - what
+//      the sweep's launch is given: the descriptor, the id table and the members' partial-sum offsets and slot counts; "desc=-": no sweep]
 //
 // and these invariants are checked on each: a step's descriptor is on exactly under its role; an absorbed step is
 // directly followed by its pair's second member or named by a complex pair's `sp`; step_off is the running sum of
@@ -37,7 +40,7 @@
 
 using namespace ctn;
 
-struct Setting { int R = 1, cu = 256, alias_ld = 0, w_ldl = 0; DevSwitches sw; };
+struct Setting { int R = 1, cu = 256, alias_ld = 0, w_ldl = 0, desc = 0; DevSwitches sw; };
 
 static bool parse_setting(const char* arg, Setting* out) {
   std::string s(arg);
@@ -51,6 +54,7 @@ static bool parse_setting(const char* arg, Setting* out) {
     else if (key == "CU") out->cu = v;
     else if (key == "ALIAS_LD") out->alias_ld = v;
     else if (key == "W_LDL") out->w_ldl = v;
+    else if (key == "DESC") out->desc = v;
     else if (key == "ZIP") d.zip = v;
     else if (key == "ZIPQ") d.zipq = v;
     else if (key == "ZIPL") d.zipl = v;
@@ -130,7 +134,18 @@ static std::string invariants(const Plan& P, const FusedForms& F) {
   return "ok";
 }
 
-static void print_line(int plan, int set, const Plan& P, const FusedForms& F) {
+// DESC=1: what the launch of the sweep would be given
+static std::string sweep_desc(const FusedForms& F) {
+  const SweepDesc& sd = F.sweep;
+  if (!sd.on) return " desc=-";
+  auto list = [](const auto& v) { std::string t; for (auto x : v) t += (t.empty() ? "" : ",") + std::to_string(x); return t; };
+  return " desc=in" + std::to_string(sd.idIn) + "/out" + std::to_string(sd.idOut) + "/S" + std::to_string(sd.sites()) + "/J" +
+         std::to_string(sd.J) + "/M" + std::to_string(sd.M) + "/D" + std::to_string(sd.D) + "/P" + std::to_string(sd.Pd) + "/ld" +
+         list(std::vector<int64_t>{sd.ldIn, sd.ldOut, sd.ldWl, sd.ldWp, sd.ldX}) + "/ids" + list(sd.ids) + "/offs" + list(F.sweep_offs) +
+         "/slots" + list(F.sweep_slots);
+}
+
+static void print_line(int plan, int set, const Plan& P, const FusedForms& F, bool desc) {
   const int n = P.n_steps;
   std::string roles, forms, lat, cplx, partials, offs, sweep, ares, dot, groups, side;
   auto item = [](std::string* to, const std::string& s) { *to += (to->empty() ? "" : ",") + s; };
@@ -153,12 +168,12 @@ static void print_line(int plan, int set, const Plan& P, const FusedForms& F) {
     if (F.zqp_side[id] >= 0) item(&side, std::to_string(id) + ":" + std::to_string(F.zqp_side[id]));
   printf("plan %d set %d rc=0 roles=%s forms=[%s] lat=[%s] cplx=[%s] partials=%s off=%s slots=%lld scratch=%lld "
          "bufs=slab:%zu,fold:%zu,zl:%lld,group:%d,sweep:%zu/%zu/%zu/%zu/%zu,tabs:%zu sweep=[%s]%s ares=[%s] dot=[%s] groups=[%s] "
-         "side=[%s]x%lldx%d %s\n",
+         "side=[%s]x%lldx%d %s%s\n",
          plan, set, roles.c_str(), forms.c_str(), lat.c_str(), cplx.c_str(), partials.c_str(), offs.c_str(), (long long)F.part_slots,
          (long long)F.scratch_need, F.slab_elems, F.fold_elems, (long long)F.zl_slab_elems, F.group_args, F.sweep_a, F.sweep_s,
          F.sweep_z, F.sweep_l, F.sweep_e, F.cplx_tabs.size(), sweep.c_str(), F.sweep.on && F.sweep.tr ? (F.sweep.f64 ? "small2f64/tr" : F.sweep.two ? "small2/tr" : "small1/tr") : !F.sweep.on ? "-" : F.sweep.small ? (F.sweep.f64 ? "small2f64" : F.sweep.two ? "small2" : "small1") : F.sweep.f64 ? "f64" : "f32",
          ares.c_str(), dot.c_str(), groups.c_str(), side.c_str(), (long long)F.zqp_side_bytes, F.zqp_side_bufs,
-         invariants(P, F).c_str());
+         invariants(P, F).c_str(), desc ? sweep_desc(F).c_str() : "");
 }
 
 int main(int argc, char** argv) {
@@ -202,7 +217,7 @@ int main(int argc, char** argv) {
     if (rc != CTN_OK) { printf("plan %d rc=%d %s\n", n_plans, rc, err.c_str()); ++n_fail; continue; }
     for (size_t j = 0; j < sets.size(); ++j) {
       // (a small-bond sweep that is asked for takes a chain plan from the chain walker: the executor's own first decision)
-      Plan Q = sweep_small_unchains(P, sets[j].sw) ? unchained(P) : P;
+      Plan Q = sweep_small_unchains(P, sets[j].R, sets[j].cu, sets[j].sw) ? unchained(P) : P;
       SweepDesc sd;
       const bool found = sweep_small_match(Q, &sd, sets[j].sw.sweep_small_tr != 0);
       if (sets[j].w_ldl > 0 && found && sd.f64)
@@ -217,7 +232,7 @@ int main(int argc, char** argv) {
       }
       const FusedForms F = fused_forms(Q, sets[j].R, sets[j].cu, sets[j].sw);
       if (invariants(Q, F) != "ok") ++n_fail;
-      print_line(n_plans, (int)j, Q, F);
+      print_line(n_plans, (int)j, Q, F, sets[j].desc != 0);
     }
   }
   return n_fail ? 1 : 0;

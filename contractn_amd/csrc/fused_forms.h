@@ -53,18 +53,20 @@ struct SweepDesc {
   std::vector<int> steps;          // the members' step indices, in chain order
   int64_t ldIn = 0, ldOut = 0, ldWl = 0, ldWp = 0, ldX = 0;
   int J = 0, M = 0, D = 0, Pd = 0;     // row blocks, rows, bond and physical dimension
-  // float64 (kernels_sweep_f64.h): the members are the 2 S steps of S sites - (GEMM, streaming sum over p) pairs, both
-  // reporting a rescale factor; ids = [S][2] tensor ids (W_s, x_s), idIn the chain's input E
-  bool f64 = false;
-  int idIn = -1;
+  // every form: ids = [S][2] tensor ids (W_s, x_s), idIn the chain's input E, idOut the last site's E'
+  int idIn = -1, idOut = -1;
   std::vector<int32_t> ids;
+  // float64 (kernels_sweep_f64.h): the members are the 2 S steps of S sites - (GEMM, streaming sum over p) pairs, both
+  // reporting a rescale factor (`two`)
+  bool f64 = false;
   // small bonds (kernels_sweep_small.h): `two` - the members are the 2 S steps of S two-step sites, as in float64; else
-  // the S epilogue-summed steps (float32 only).  ids and idIn are filled in both shapes.  small && f64: k_sweep_small<double>,
-  // always `two`.
+  // the S epilogue-summed steps (float32 only).  small && f64: k_sweep_small<double>, always `two`.
   // tr (small only): every core of the run is stored TRANSPOSED - the bond contracted with the state is its unit-stride
   // axis and the bond it keeps has the stride ldWl (k_sweep_small<.., TR = true>); else the kept bond is unit-stride and
   // ldWl is the contracted one's.  ldWl is the stride of the core's non-unit bond either way.
   bool small = false, two = false, tr = false;
+  int entries() const { return two ? 2 : 1; }                     // member steps - and abs-sum records - per site
+  int sites() const { return (int)steps.size() / entries(); }
 };
 // A full dot of a tensor with a transposed one (k_dot_tr), found on the plan's tables
 struct DotTr { bool on = false; int Ka = 0, Kb = 0, x_is_a = 1; int64_t ldY = 0; };
@@ -164,11 +166,16 @@ inline bool zipq_fits(const ZipDesc& z) {
 // at every one of its shapes, and the complex GPU suite has to be green with CTN_CPLX=1.
 static constexpr bool kCplxDefault = false;
 
-// Is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
+// One site of a sweep, E'[b, r] = sum_p x[b, p] sum_l E[b, l] W[l, p, r], as either reader below finds it in the plan: the
+// tensors, the row strides of E (ldA), E' (ldC) and x, the core's two non-unit strides, rows, bond and physical dimension,
+// whether the core is stored transposed (SweepDesc::tr) and the site's member steps - sa alone, or the pair (sa, sb).
+struct SweepSite { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0;
+                   int D = 0, Pd = 0; bool tr = false; int sa = -1, sb = -1; };
+
+// The one-step reader: is step s an epilogue-summed GEMM step that k_sweep_f32 can take as one site of a sweep?  Checked on the plan's own
 // offset tables: E row-major [b][l], W[l][p][r] with r unit-stride, x[b][p] with p unit-stride, result rows [b][r].
 // `small`: as one site of k_sweep_small<float> instead - any bond 8 ... 64 that is a multiple of 4, x rows of any stride >= |p|.
-struct SweepShape { int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; bool tr = false; };
-inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh, bool small = false) {
+inline bool sweep_site_one(const Plan& P, int s, SweepSite* sh, bool small) {
   const Step& st = P.steps[s];
   const int D = (int)st.K, Pd = st.epw;
   const bool bond_ok = small ? (st.K >= 8 && st.K <= 64 && st.K % 4 == 0) : (st.K == 64 || st.K == 128 || st.K == 256 || st.K == 512);
@@ -221,72 +228,13 @@ inline bool sweep_step_shape(const Plan& P, int s, SweepShape* sh, bool small = 
   // a lane's offsets into a core: 32 bits.  (Transposed: the largest is row D - 1 of r, p = 3 and the lane's four values
   // of l, ((D - 1) ldWl + 3 ldWp + 12) 4 bytes - below the same bound, which is kept for both.)
   if (((D + 12) * ldWl + 3 * ldWp + D) * 4 >= ((int64_t)1 << 31)) return false;
-  sh->tr = tr;
+  sh->tr = tr; sh->sa = sh->sb = s;
+  sh->idE = st.lhs; sh->idW = st.rhs; sh->idX = st.lhs2; sh->idOut = st.out;
   sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = D; sh->Pd = Pd;
   return true;
 }
 
-// The longest run of such steps, each taking the result of the one before as its E.  (`small`: see sweep_step_shape.)
-inline bool sweep_match(const Plan& P, SweepDesc* d, bool small = false) {
-  std::vector<int> best;
-  SweepShape best_first, best_last;
-  std::vector<char> used((size_t)P.n_steps, 0);
-  for (int s0 = 0; s0 < P.n_steps; ++s0) {
-    SweepShape first, cur, last;
-    if (used[s0] || !sweep_step_shape(P, s0, &first, small)) continue;
-    std::vector<int> run{s0};
-    last = first;
-    for (int s = s0 + 1; s < P.n_steps; ++s) {
-      // Only markers of absorbed steps (nothing is launched for them) may lie between two members: the ONE launch of
-      // the run sits at its last member's position and reads the first member's input there, which the plan's arena
-      // released right after the first member - any launched step in between (the other half of an interleaved
-      // left / right chain, say) could have been given that region.  Such a step ends the run.
-      if (P.steps[s].kernel == CTN_KERNEL_FUSED) continue;
-      if (P.steps[s].lhs != P.steps[run.back()].out && P.steps[s].rhs != P.steps[run.back()].out &&
-          P.steps[s].lhs2 != P.steps[run.back()].out)
-        break;
-      // the consumer of the run's last result: a member if it has the same shape and takes it as its E
-      if (P.steps[s].lhs == P.steps[run.back()].out && sweep_step_shape(P, s, &cur, small) && cur.M == first.M && cur.D == first.D &&
-          cur.Pd == first.Pd && cur.ldWl == first.ldWl && cur.ldWp == first.ldWp && cur.ldX == first.ldX && cur.ldA == last.ldC &&
-          cur.tr == first.tr) {                    // (a core stored the other way round ends the run)
-        run.push_back(s);
-        last = cur;
-        continue;
-      }
-      break;
-    }
-    for (int s : run) used[s] = 1;
-    if (run.size() > best.size()) { best = run; best_first = first; best_last = last; }
-  }
-  if (best.size() < 2) return false;
-  {
-    // the run's result must not land on its own input: blocks of rows start and finish at different times (a launch of
-    // more than one round of workgroups), so a block's result rows may only cover ITS OWN input rows - the same region
-    // with the same row stride - or nothing of the input at all
-    const int idIn = P.steps[best.front()].lhs, idOut = P.steps[best.back()].out;
-    const bool in_ws = idIn >= P.n_inputs, out_ws = idOut < P.n_inputs + P.n_steps - 1;
-    if (in_ws && out_ws) {
-      const int64_t es = P.elem_size();
-      const int64_t a0 = P.tensors[idIn].ws_offset, a1 = a0 + ((best_first.M - 1) * best_first.ldA + best_first.D) * es;
-      const int64_t b0 = P.tensors[idOut].ws_offset, b1 = b0 + ((best_first.M - 1) * best_last.ldC + best_first.D) * es;
-      const bool overlap = a0 < b1 && b0 < a1;
-      if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
-    }
-  }
-  d->on = true; d->steps = best; d->small = small; d->tr = best_first.tr;
-  if (small) {
-    d->idIn = P.steps[best.front()].lhs;
-    for (int s : best) { d->ids.push_back(P.steps[s].rhs); d->ids.push_back(P.steps[s].lhs2); }
-  }
-  d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
-  d->J = (int)((best_first.M + kFormSWR - 1) / kFormSWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
-  return true;
-}
-
-// Is k_sweep_f64 taken without CTN_SWEEP=1?  Decided by measurement (DESIGN section 10).
-static constexpr bool kSweepF64Default = false;
-
-// The float64 plan keeps a site as TWO steps (plan.cpp fuses them for fp32 only): sa a GEMM of E[b, l] with a network
+// The two-step reader: the float64 plan keeps a site as TWO steps (plan.cpp fuses them for fp32 only): sa a GEMM of E[b, l] with a network
 // input W carrying {l, p, r}, sb the streaming step that sums p against a network input x[b, p].  Can k_sweep_f64 take
 // the pair as one site?  Matched on the tensors' labels, dims and strides: E and E' row-major [b][.], r unit-stride in W,
 // p unit-stride in x, every stride even (16-byte accesses).  The layout the planner gave C does not matter: C is never
@@ -299,11 +247,10 @@ static constexpr bool kSweepF64Default = false;
 // rows of any stride >= |p| (8-byte loads), and every stride of E, E' and W even.  (`small` takes the plan's own type,
 // float32 or float64 and nothing else.)  Why, stride by stride - the kernel's own accesses are all 8-byte: ldC (E') because k_sweep64_finish<double> rewrites
 // the result's rows as double2; ldA (E) because a member's E is the E' of the site before (cur.ldA == last.ldC) and the run's
-// input may be the very region its result lands on, with the same row stride (the aliasing rule below) - one parity for
+// input may be the very region its result lands on, with the same row stride (the aliasing rule of sweep_run) - one parity for
 // both; ldWl and ldWp so that each 128-byte run that the 16 lanes of a group read of a core starts 16-byte aligned, as
 // k_sweep_f64's own condition has it (a bond-64 plan is refused by both kernels or by neither on its strides).
-struct Sweep64Site { int idE = -1, idW = -1, idX = -1, idOut = -1; int64_t ldA = 0, ldC = 0, ldWl = 0, ldWp = 0, ldX = 0, M = 0; int D = 0, Pd = 0; bool tr = false; };
-inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, bool small = false) {
+inline bool sweep_site_two(const Plan& P, int sa, int sb, SweepSite* sh, bool small) {
   if ((P.dtype != CTN_F64 && !(small && P.dtype == CTN_F32)) || sb + 1 >= P.n_steps) return false;   // a step must follow the last member
   const Step& a = P.steps[sa];
   const Step& b = P.steps[sb];
@@ -348,57 +295,66 @@ inline bool sweep64_site_shape(const Plan& P, int sa, int sb, Sweep64Site* sh, b
   // p = 3 and the lane's place in a group, ((D - 1) ldWl + 3 ldWp + 12) 4 or ((D - 1) ldWl + 3 ldWp + 3) 8 bytes - both
   // below the same bound.)
   if ((D + 12) * ldWl + 3 * ldWp + D >= ((int64_t)1 << 28)) return false;
-  sh->tr = tr;
+  sh->tr = tr; sh->sa = sa; sh->sb = sb;
   sh->idE = idE; sh->idW = idW; sh->idX = idX; sh->idOut = b.out;
   sh->ldA = ldA; sh->ldC = ldC; sh->ldWl = ldWl; sh->ldWp = ldWp; sh->ldX = ldX; sh->M = M; sh->D = (int)D; sh->Pd = (int)Pd;
   return true;
 }
 
-// The longest run of such pairs, each taking the result of the one before as its E.  The two safety rules are those of
-// sweep_match: nothing that is launched may lie between two members, and the run's result may overlap its input only as
-// the same region with the same row stride.
-inline bool sweep64_match(const Plan& P, SweepDesc* d, bool small = false) {
+// The longest run of sites, each taking the result of the one before as its E - `two`: of (GEMM, streaming) pairs, as
+// sweep_site_two reads them, else of epilogue-summed steps (sweep_site_one); `small`: see the readers - and the ONE place
+// that fills a SweepDesc.  Steps that launch nothing (CTN_KERNEL_FUSED, the markers of absorbed steps) are stepped over.
+inline bool sweep_run(const Plan& P, SweepDesc* d, bool two, bool small) {
   auto next_launched = [&](int s) { do ++s; while (s < P.n_steps && P.steps[s].kernel == CTN_KERNEL_FUSED); return s; };
-  std::vector<int> best;
-  std::vector<int32_t> best_ids;
-  Sweep64Site best_first, best_last;
+  auto site_at = [&](int sa, SweepSite* sh) {
+    if (sa >= P.n_steps || P.steps[sa].kernel == CTN_KERNEL_FUSED) return false;
+    if (!two) return sweep_site_one(P, sa, sh, small);
+    const int sb = next_launched(sa);
+    return sb < P.n_steps && sweep_site_two(P, sa, sb, sh, small);
+  };
+  std::vector<SweepSite> best;
   std::vector<char> used((size_t)P.n_steps, 0);
   for (int s0 = 0; s0 < P.n_steps; ++s0) {
-    Sweep64Site first, cur, last;
-    int sb = next_launched(s0);
-    if (used[s0] || P.steps[s0].kernel == CTN_KERNEL_FUSED || sb >= P.n_steps || !sweep64_site_shape(P, s0, sb, &first, small)) continue;
-    std::vector<int> run{s0, sb};
-    std::vector<int32_t> ids{first.idW, first.idX};
-    last = first;
-    for (;;) {
-      const int na = next_launched(run.back());
-      const int nb = na < P.n_steps ? next_launched(na) : na;
-      if (nb >= P.n_steps || !sweep64_site_shape(P, na, nb, &cur, small) || cur.idE != last.idOut || cur.M != first.M || cur.D != first.D ||
-          cur.Pd != first.Pd || cur.ldWl != first.ldWl || cur.ldWp != first.ldWp || cur.ldX != first.ldX || cur.ldA != last.ldC ||
-          cur.tr != first.tr)                      // (a core stored the other way round ends the run)
-        break;
-      run.push_back(na); run.push_back(nb);
-      ids.push_back(cur.idW); ids.push_back(cur.idX);
-      last = cur;
-    }
-    for (int s : run) used[s] = 1;
-    if (run.size() > best.size()) { best = run; best_ids = ids; best_first = first; best_last = last; }
+    SweepSite first, cur;
+    if (used[s0] || !site_at(s0, &first)) continue;
+    std::vector<SweepSite> run{first};
+    // Only markers of absorbed steps (nothing is launched for them) may lie between two members: the ONE launch of
+    // the run sits at its last member's position and reads the first member's input there, which the plan's arena
+    // released right after the first member - any launched step in between (the other half of an interleaved
+    // left / right chain, say) could have been given that region.  So the next LAUNCHED step is a member - it takes the
+    // run's last result as its E and has the same shape - or ends the run.
+    while (site_at(next_launched(run.back().sb), &cur) && cur.idE == run.back().idOut && cur.M == first.M && cur.D == first.D &&
+           cur.Pd == first.Pd && cur.ldWl == first.ldWl && cur.ldWp == first.ldWp && cur.ldX == first.ldX && cur.ldA == run.back().ldC &&
+           cur.tr == first.tr)                      // (a core stored the other way round ends the run)
+      run.push_back(cur);
+    for (const SweepSite& m : run) used[m.sa] = used[m.sb] = 1;
+    if (run.size() > best.size()) best = run;
   }
-  if (best.size() < 4) return false;            // at least 2 sites
+  if (best.size() < 2) return false;
+  const SweepSite &first = best.front(), &last = best.back();
   {
-    const int idIn = best_first.idE, idOut = best_last.idOut;
-    const bool in_ws = idIn >= P.n_inputs, out_ws = idOut < P.n_inputs + P.n_steps - 1;
+    // the run's result must not land on its own input: blocks of rows start and finish at different times (a launch of
+    // more than one round of workgroups), so a block's result rows may only cover ITS OWN input rows - the same region
+    // with the same row stride - or nothing of the input at all
+    const bool in_ws = first.idE >= P.n_inputs, out_ws = last.idOut < P.n_inputs + P.n_steps - 1;
     if (in_ws && out_ws) {
       const int64_t es = P.elem_size();
-      const int64_t a0 = P.tensors[idIn].ws_offset, a1 = a0 + ((best_first.M - 1) * best_first.ldA + best_first.D) * es;
-      const int64_t b0 = P.tensors[idOut].ws_offset, b1 = b0 + ((best_first.M - 1) * best_last.ldC + best_first.D) * es;
+      const int64_t a0 = P.tensors[first.idE].ws_offset, a1 = a0 + ((first.M - 1) * first.ldA + first.D) * es;
+      const int64_t b0 = P.tensors[last.idOut].ws_offset, b1 = b0 + ((first.M - 1) * last.ldC + first.D) * es;
       const bool overlap = a0 < b1 && b0 < a1;
-      if (overlap && !(a0 == b0 && best_first.ldA == best_last.ldC)) return false;
+      if (overlap && !(a0 == b0 && first.ldA == last.ldC)) return false;
     }
   }
-  d->on = true; d->f64 = P.dtype == CTN_F64; d->small = small; d->two = true; d->tr = best_first.tr; d->steps = best; d->ids = best_ids; d->idIn = best_first.idE;
-  d->ldIn = best_first.ldA; d->ldOut = best_last.ldC; d->ldWl = best_first.ldWl; d->ldWp = best_first.ldWp; d->ldX = best_first.ldX;
-  d->J = (int)((best_first.M + kFormSWR - 1) / kFormSWR); d->M = (int)best_first.M; d->D = best_first.D; d->Pd = best_first.Pd;
+  SweepDesc r;
+  r.on = true; r.f64 = P.dtype == CTN_F64; r.small = small; r.two = two; r.tr = first.tr; r.idIn = first.idE; r.idOut = last.idOut;
+  for (const SweepSite& m : best) {
+    r.steps.push_back(m.sa);
+    if (two) r.steps.push_back(m.sb);
+    r.ids.push_back(m.idW); r.ids.push_back(m.idX);
+  }
+  r.ldIn = first.ldA; r.ldOut = last.ldC; r.ldWl = first.ldWl; r.ldWp = first.ldWp; r.ldX = first.ldX;
+  r.J = (int)((first.M + kFormSWR - 1) / kFormSWR); r.M = (int)first.M; r.D = first.D; r.Pd = first.Pd;
+  *d = r;
   return true;
 }
 
@@ -413,18 +369,16 @@ static constexpr bool kSweepSmallDefault = false;
 static constexpr bool kSweepSmallF64Default = false;
 
 // A batched MPS of bond 8 ... 64 (kernels_sweep_small.h).  Float32, in either shape the planner gives its sites: the longest
-// run of two-step sites (sweep64_match on the float32 plan) or of epilogue-summed steps (sweep_match at the small bonds),
-// whichever walks more sites.  Float64: the longest run of two-step sites - the one shape a float64 plan has.  Both
-// matchers keep their two safety rules: nothing launched between members, and the run's result overlaps its input only
-// as the same region with the same row stride.  At most kFormSweepMaxSites sites.
+// run of two-step sites or of epilogue-summed steps, whichever walks more sites.  Float64: the longest run of two-step
+// sites - the one shape a float64 plan has.  At most kFormSweepMaxSites sites.
 // `tr_ok` false (CTN_SWEEP_SMALL_TR=0): a run of transposed cores is not taken.
 inline bool sweep_small_match(const Plan& P, SweepDesc* d, bool tr_ok = true) {
   if (P.dtype != CTN_F32 && P.dtype != CTN_F64) return false;
   SweepDesc two, one;
-  const bool m2 = sweep64_match(P, &two, true) && (tr_ok || !two.tr), m1 = P.dtype == CTN_F32 && sweep_match(P, &one, true) && (tr_ok || !one.tr);
+  const bool m2 = sweep_run(P, &two, true, true) && (tr_ok || !two.tr), m1 = P.dtype == CTN_F32 && sweep_run(P, &one, false, true) && (tr_ok || !one.tr);
   if (!m1 && !m2) return false;
-  *d = (m2 && (!m1 || two.steps.size() / 2 >= one.steps.size())) ? two : one;
-  return (int)(d->two ? d->steps.size() / 2 : d->steps.size()) <= kFormSweepMaxSites;
+  *d = (m2 && (!m1 || two.sites() >= one.sites())) ? two : one;
+  return d->sites() <= kFormSweepMaxSites;
 }
 
 // Is the small-bond sweep asked for on this plan?  Only on request while its type's default is off - float32:
@@ -436,20 +390,35 @@ inline bool sweep_small_asked(const Plan& P, const DevSwitches& sw) {
   return P.dtype == CTN_F64 && sw.sweep64 != 0 && (sw.sweep_small64 == 1 || (kSweepSmallF64Default && sw.sweep_small64 != 0));
 }
 
-// Does k_sweep_f64 take the plan (CTN_SWEEP=1, bond 64 ... 512, MFMA-sized steps)?  Its run is never the small form's.
-inline bool sweep64_takes(const Plan& P, const DevSwitches& sw, SweepDesc* d) {
-  return P.dtype == CTN_F64 && sw.sweep != 0 && P.stabilize && sw.sweep64 != 0 && (sw.sweep == 1 || kSweepF64Default) &&
-         sweep64_match(P, d) && (int)d->steps.size() <= 2 * kFormSweepMaxSites;
+// Is k_sweep_f64 taken without CTN_SWEEP=1?  Decided by measurement (DESIGN section 10).
+static constexpr bool kSweepF64Default = false;
+
+// Which sweep takes the plan, if any: the ONE place that states the forms' precedence.  Never against CTN_SWEEP=0, and only
+// while the plan rescales.  First k_sweep_f32, at least half a chip of row blocks, or CTN_SWEEP=1; then k_sweep_f64
+// (CTN_SWEEP=1 and not CTN_SWEEP64=0; bond 64 ... 512, MFMA-sized steps: its run is never the small form's); then, only where
+// neither took the plan and only on request (sweep_small_asked), the small-bond form of the plan's type.
+inline bool sweep_form(const Plan& P, int R, int n_cu, const DevSwitches& sw, SweepDesc* d) {
+  if (sw.sweep == 0 || !P.stabilize) return false;
+  // (bonds up to 128: the per-site launches are a few microseconds of latency each whatever the batch - always)
+  if (sweep_run(P, d, false, false) && d->sites() <= kFormSweepMaxSites &&
+      (sw.sweep == 1 || (d->steps.size() >= 4 && (d->D <= 128 || (int64_t)d->J * R * 2 >= n_cu))))
+    return true;
+  if (P.dtype == CTN_F64 && sw.sweep64 != 0 && (sw.sweep == 1 || kSweepF64Default) && sweep_run(P, d, true, false) &&
+      (int)d->steps.size() <= 2 * kFormSweepMaxSites)
+    return true;
+  if (sweep_small_asked(P, sw) && sweep_small_match(P, d, sw.sweep_small_tr != 0)) return true;
+  *d = SweepDesc();
+  return false;
 }
 
 // A chain plan (Plan::chain: every step small) is walked whole by the chain walker and has no fused form - most
-// small-bond classifiers with a batch of a few dozen are such plans.  A small-bond sweep that is asked for and matches
-// takes the plan from the walker: the executor (and forms_check) then works on a copy whose steps are launches of their
-// own again, with the slot counts and collapse flags the planner gave them before it marked the plan.
-// On a float64 plan (CTN_SWEEP_SMALL64=1) only where k_sweep_f64 would not take the un-chained plan.
-inline bool sweep_small_unchains(const Plan& P, const DevSwitches& sw) {
-  SweepDesc d, k64;
-  return P.chain && sweep_small_asked(P, sw) && sweep_small_match(P, &d, sw.sweep_small_tr != 0) && !sweep64_takes(P, sw, &k64);
+// small-bond classifiers with a batch of a few dozen are such plans.  A small-bond sweep that is asked for and takes the
+// plan (sweep_form: on a float64 plan only where k_sweep_f64 does not; no step of a chain plan is epilogue-summed, so
+// k_sweep_f32 never does) takes it from the walker: the executor (and forms_check) then works on a copy whose steps are
+// launches of their own again, with the slot counts and collapse flags the planner gave them before it marked the plan.
+inline bool sweep_small_unchains(const Plan& P, int R, int n_cu, const DevSwitches& sw) {
+  SweepDesc d;
+  return P.chain && sweep_form(P, R, n_cu, sw, &d) && d.small;
 }
 inline Plan unchained(const Plan& P) {
   Plan Q = P;
@@ -787,35 +756,20 @@ inline FusedForms fused_forms(const Plan& P, int R, int n_cu, const DevSwitches&
       F.ares_ntw[s] = ares_match(P, s, R, n_cu, sw);
       if (F.ares_ntw[s] && ares_avec(P, s)) F.ares_ntw[s] |= 1 << 16;
     }
-  // a sweep: at least half a chip of row blocks, or CTN_SWEEP=1; at the small bonds only on request (CTN_SWEEP_SMALL=1,
-  // float64: CTN_SWEEP_SMALL64=1)
-  if (sw.sweep != 0 && P.stabilize) {
-    SweepDesc sd;
-    // (bonds up to 128: the per-site launches are a few microseconds of latency each whatever the batch - always)
-    if (sweep_match(P, &sd) && (int)sd.steps.size() <= kFormSweepMaxSites &&
-        (sw.sweep == 1 || (sd.steps.size() >= 4 && (sd.D <= 128 || (int64_t)sd.J * R * 2 >= n_cu)))) {
-      const size_t S = sd.steps.size(), nrec = (size_t)R * S * sd.J;
-      for (int s : sd.steps) { F.sweep_ids.push_back(P.steps[s].rhs); F.sweep_ids.push_back(P.steps[s].lhs2); }
-      F.sweep_a = nrec; F.sweep_s = nrec; F.sweep_z = (size_t)R * S; F.sweep_l = nrec;
-      F.sweep = sd;
-    } else if (sweep64_takes(P, sw, &sd)) {
-      // float64 (k_sweep_f64): the run's 2 S steps are all members - a GEMM and a streaming step per site
-      const size_t T = sd.steps.size(), nrec = (size_t)R * (T / 2) * sd.J;
-      F.sweep_ids = sd.ids;
-      F.sweep_a = 2 * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * T;
-      F.sweep = sd;
-    } else if (SweepDesc ss; sweep_small_asked(P, sw) && sweep_small_match(P, &ss, sw.sweep_small_tr != 0)) {
-      // small bonds (k_sweep_small, either type), only where neither form above took the plan: a record per (site, row
-      // block) and member entry - two per site of the two-step shape (float64: always), one of the epilogue-summed shape
-      const size_t S = ss.two ? ss.steps.size() / 2 : ss.steps.size(), nrec = (size_t)R * S * ss.J;
-      F.sweep_ids = ss.ids;
-      F.sweep_a = (ss.two ? 2 : 1) * nrec; F.sweep_e = nrec; F.sweep_z = (size_t)R * ss.steps.size();
-      F.sweep = ss;
-    }
-    for (int s : F.sweep.steps) {
-      F.sweep_role[s] = s == F.sweep.steps.back() ? 2 : 1;
+  // a sweep, in whichever form takes the plan (sweep_form).  Its records, per replica: an abs-sum per (member entry of a
+  // site, row block) and a factor per member step; k_sweep_f32 keeps a scale and two logs per (site, row block) beside them,
+  // the other forms an exponent
+  if (SweepDesc sd; sweep_form(P, R, n_cu, sw, &sd)) {
+    const size_t nrec = (size_t)R * sd.sites() * sd.J;
+    F.sweep_a = sd.entries() * nrec; F.sweep_z = (size_t)R * sd.steps.size();
+    if (sd.f64 || sd.small) F.sweep_e = nrec;
+    else F.sweep_s = F.sweep_l = nrec;
+    F.sweep_ids = sd.ids;
+    for (int s : sd.steps) {
+      F.sweep_role[s] = s == sd.steps.back() ? 2 : 1;
       F.sweep_offs.push_back(F.step_off[s]); F.sweep_slots.push_back(F.step_partials[s]);
     }
+    F.sweep = sd;
   }
   // leaf groups: runs of consecutive plain streaming steps on network inputs, same kernel variant (see LeafGroup)
   if (sw.group) {

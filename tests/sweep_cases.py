@@ -9,7 +9,7 @@ One site of the chain is
 
 (two pairwise steps of the path; the planner folds them into ONE epilogue-summed GEMM step (B, D P, D) behind an absorbed
 marker step) and every network ends with a probe step  out[b, w] = sum_r E'[b, r] Pr[r, w],  Pr a signed permutation: a
-step is a sweep member only when a step follows it (engine.hip, sweep_step_shape), and this one is exact in fp32 - `out`
+step is a sweep member only when a step follows it (fused_forms.h, sweep_site_one), and this one is exact in fp32 - `out`
 is E' with its columns permuted and some of them negated: B x D values per replica.
 
 Operands, in this order:

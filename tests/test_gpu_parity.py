@@ -1527,7 +1527,7 @@ def test_sweep_is_not_taken_across_interleaved_chains(batch, monkeypatch):
     """Two batched MPS hanging on one batch hyperedge, walked ALTERNATELY (a site of chain A, a site of chain B, ...):
     between two members of either chain lies a launched step of the other, whose result the arena may place where the
     chain's first input was (released right after its first member).  A sweep launches at its last member's position and
-    reads that input there - so such a run must not be taken (round-3 advice, engine.hip sweep_match).  With CTN_SWEEP=1
+    reads that input there - so such a run must not be taken (round-3 advice, fused_forms.h sweep_run).  With CTN_SWEEP=1
     the value must be the per-site launches' and the oracle's, and no step may report the sweep's tile."""
     from contractn_amd.paths import ssa_to_linear
     from contractn_amd.utils import get_symbol
